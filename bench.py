@@ -12,8 +12,14 @@ With N > 1 ranks the full assignments are then all-gathered over RCCL.
 Weak scaling: per-rank batch fixed.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+                    [--dump-outputs DIR] [--full]
 
-Rank 0 prints ONE JSON line.  After the timed region (untimed): the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K
+steps and prints the headline (value, ms_per_step, the step-time spread).
+--dump-outputs DIR writes the assignments of the last timed step as
+DIR/assignments.npy (the inputs are seeded: the same arguments give the same
+inputs and, on the same build, the same file).  With --full, after the timed
+region (untimed): the stage / host breakdown and the roofline, the
 precompiled-request rate, the admission loop (gather, Fits + AddUsage in
 order on rank 0, delta broadcast, replicas apply), the whole timed batch
 checked against the CPU oracle, the oracle's CPU baseline, the adversarial
@@ -41,10 +47,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="C3")
     ap.add_argument("--batch", type=int, default=1024, help="pending workloads per rank per step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's assignments to DIR/assignments.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs: stage breakdown, roofline, precompiled rate, admission loop, "
+                         "CPU baseline + whole-batch oracle check, C3J and the widened rows")
     ap.add_argument("--cpu-sample", type=int, default=64, help="workloads timed on the single-thread CPU oracle")
     ap.add_argument("--parity-threads", type=int, default=16, help="oracle threads for the whole-batch check")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and the whole-batch oracle check")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C3J variant and the widened rows")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the whole-batch oracle check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the C3J variant and the widened rows")
     return ap.parse_args()
 
 
@@ -189,6 +200,24 @@ def place_host(gpu, local_rank):
         return None
 
 
+DUMP_CAP_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, quads, cap_bytes=DUMP_CAP_BYTES):
+    """The timed path's output (the int32 assignment quads a caller of
+    run_compiled reads back: per workload (id, -1, failed, n), then
+    (id, podset, leaf, count) per assigned domain) as DIR/assignments.npy,
+    float64 [rows, 4].  Above the size cap a fixed, seeded sample of rows."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    rows = np.asarray(quads, dtype=np.float64).reshape(-1, 4)
+    cap = (cap_bytes - 128) // (4 * 8)  # the file: 128 bytes of .npy header, then the rows
+    if rows.shape[0] > cap:
+        rows = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], size=cap, replace=False))]
+    np.save(os.path.join(path, "assignments.npy"), rows)
+
+
 def heartbeat(period=30.0):
     """A progress line on stderr every `period` s (long setup / oracle phases
     of the 1M-node config print nothing else for minutes)."""
@@ -314,9 +343,49 @@ def main():
     dt = time.perf_counter() - t0
     timed_stages, timed_runs, timed_fills = snap.stage_accum(reset=True)
     snap.set_stage_timing(True)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, snap.last_assignments())
     if plus[0]:
         snap.apply_deltas(neg_deltas)  # back to S for everything below
     per_step = [x * 1e3 for x in per_step]
+    if dist is not None:
+        tt = torch.tensor([dt], dtype=torch.float64, device=device)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+    placements = len(all_wls) * a.steps  # every rank's shard, all steps
+    value = placements / dt
+    line = {
+        "metric": "TAS placements/sec at 128k nodes (1/2/4/8 GPU); % HBM roofline",
+        "value": round(value, 1),
+        "unit": "placements/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(dt / a.steps * 1e3, 3),
+        "step_ms": {"median": round(pct(per_step, 0.5), 3), "p10": round(pct(per_step, 0.1), 3),
+                    "p90": round(pct(per_step, 0.9), 3), "max": round(max(per_step), 3),
+                    "over_1ms": sum(1 for x in per_step if x > 1.0)},
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic (seeded generator modelled on test/performance/scheduler/generator)",
+        "config": {"workload": f"{a.config}: {N} nodes, {a.batch} pending workloads per GPU per step from "
+                               "TASPodSetRequests (grouping + request compile + evaluation + TopologyAssignment "
+                               "values in the step; 50% BestFit required/preferred, 50% LeastFreeCapacity "
+                               "unconstrained; taints + nodeSelector)",
+                   "nodes": N, "batch_per_gpu": a.batch, "parallelism": f"dp{world} (replicated snapshot)"},
+        "setup_s": {"generate": round(gen_s, 2), "snapshot_load_and_compile": round(load_s, 2)},
+        "host_placement": {"l3_cpus": placed, "note": "rank's main thread bound to one L3 domain on the "
+                           "GPU's NUMA node; the library pins its host pool to that L3's other cores"},
+    }
+    if not a.full:  # a plain run ends with the headline
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        snap.close()
+        return
     # stage / host breakdown from the same step, in untimed repeats (their
     # ctypes getters stay out of the timed loop)
     stage_sum, dev_host_sum, detail_sum = {}, {}, {}
@@ -331,12 +400,6 @@ def main():
         for k, v in snap.last_host_detail().items():
             detail_sum[k] = detail_sum.get(k, 0.0) + v
     barrier()
-    if dist is not None:
-        tt = torch.tensor([dt], dtype=torch.float64, device=device)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
-    placements = len(all_wls) * a.steps  # every rank's shard, all steps
-    value = placements / dt
     st, fill_bytes, per_launch_fill_ms, achieved, R_used = roofline_of(snap, snap_doc, mine, a.steps, stage_sum)
     # the roofline's duration: the fill launches of the timed steps themselves
     timed_fill_ms = timed_stages["fill"] / max(timed_fills, 1)
@@ -434,27 +497,7 @@ def main():
     host["staging_detail_ms"] = {k: round(v / a.steps, 3) for k, v in detail_sum.items()}
     traffic, traffic_src = load_traffic(os.path.join(ROOT, "profiles", "fill_traffic.json"), a.config)
     if rank == 0:
-        line = {
-            "metric": "TAS placements/sec at 128k nodes (1/2/4/8 GPU); % HBM roofline",
-            "value": round(value, 1),
-            "unit": "placements/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 3),
-            "step_ms": {"median": round(pct(per_step, 0.5), 3), "p10": round(pct(per_step, 0.1), 3),
-                        "p90": round(pct(per_step, 0.9), 3), "max": round(max(per_step), 3),
-                        "over_1ms": sum(1 for x in per_step if x > 1.0)},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic (seeded generator modelled on test/performance/scheduler/generator)",
-            "config": {"workload": f"{a.config}: {N} nodes, {a.batch} pending workloads per GPU per step from "
-                                   "TASPodSetRequests (grouping + request compile + evaluation + TopologyAssignment "
-                                   "values in the step; 50% BestFit required/preferred, 50% LeastFreeCapacity "
-                                   "unconstrained; taints + nodeSelector)",
-                       "nodes": N, "batch_per_gpu": a.batch, "parallelism": f"dp{world} (replicated snapshot)"},
+        line.update({
             "roofline": {"kernel": "fill_pair_kernel" if st.get("fill_paths", 0) & 8192 else "fill_leaves_staged_kernel",
                          "bound": "hbm", "achieved": round(achieved_timed, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved_timed / HBM_PEAK_GBS, 4),
@@ -492,10 +535,7 @@ def main():
             "cpu_baseline": cpu,
             "parity_full_batch": parity,
             "extras": extras,
-            "setup_s": {"generate": round(gen_s, 2), "snapshot_load_and_compile": round(load_s, 2)},
-            "host_placement": {"l3_cpus": placed, "note": "rank's main thread bound to one L3 domain on the "
-                               "GPU's NUMA node; the library pins its host pool to that L3's other cores"},
-        }
+        })
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

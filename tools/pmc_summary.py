@@ -12,8 +12,8 @@ quad-cycles (MI355X_MICROARCH.md PMC table).  Writes the table to
 <out>/pmc_summary.json and the fill kernel's bytes per launch to
 profiles/fill_traffic.json, which bench.py reports as roofline.traffic.
 
-    python tools/pmc_summary.py gpurun_out profiles/r01 C3
-    python tools/pmc_summary.py gpurun_out profiles/r04 C3J _c3j   (tools/pmc.sh _c3j passes;
+    python tools/pmc_summary.py bench_out profiles/r01 C3
+    python tools/pmc_summary.py bench_out profiles/r04 C3J _c3j   (tools/pmc.sh _c3j passes;
         writes pmc_summary_c3j.json, fill_traffic.json only for C3)
 """
 import csv
