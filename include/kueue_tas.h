@@ -401,6 +401,37 @@ int kueue_tas_fits(kueue_tas_ctx* ctx, const kueue_tas_fits_req* reqs, size_t n,
  * pods_col; -1: no pods column).  Every term's col must be >= 0. */
 int kueue_tas_admit(kueue_tas_ctx* ctx, const kueue_tas_fits_req* reqs, size_t n, const kueue_tas_fits_term* terms,
                     size_t num_terms, const int64_t* wl_off, size_t n_workloads, int32_t pods_col, int32_t* admitted);
+/* kueue_tas_admit for a cycle whose entries carry preemption targets
+ * (processEntry :419-435 with fits() :621-629): one call = the cycle's ordered
+ * entry list.  The n_targets preemptable workloads are given by their usage
+ * as delta records (what RemoveUsage subtracts: the records
+ * kueue_tas_host_last_deltas emitted when the workload was admitted), target t
+ * owning target_deltas[target_off[t] .. target_off[t+1]); entry w lists the
+ * targets entry_targets[entry_target_off[w] .. entry_target_off[w+1]).  With
+ * P = {} at the start, for w in order:
+ *   a target of w is in P                       -> verdict[w] = 2 (skipped,
+ *       "overlapping preemption targets"); nothing changes;
+ *   else every record of w fits (kueue_tas_fits' rules) against tas_usage
+ *   minus the usage of P and of w's targets
+ *   (SimulateWorkloadRemoval, snapshot.go:67-84 -> removeTASUsage
+ *   tas_flavor_snapshot.go:281-293; a removed key counts as present, as after
+ *   Requests.Sub; a target record with leaf -1 is skipped)
+ *                                               -> verdict[w] = 1, P += w's
+ *       targets, w's usage added as kueue_tas_admit adds it;
+ *   else                                        -> verdict[w] = 0, P unchanged.
+ * So a later entry without targets is checked with the earlier entries'
+ * targets removed as well.  After the call tas_usage is the usage before it
+ * plus the verdict-1 entries' usage, bit for bit: every target's usage is
+ * back (the caller removes a preempted workload's usage when it is evicted).
+ * KUEUE_TAS_EINVAL, with the snapshot untouched, for offsets that are not
+ * monotone, a target id outside [0, n_targets), a target listed twice by one
+ * entry, a target record's leaf outside [-1, N) or column outside [0, R).
+ * When no entry lists a target the call is kueue_tas_admit. */
+int kueue_tas_admit_targets(kueue_tas_ctx* ctx, const kueue_tas_fits_req* reqs, size_t n,
+                            const kueue_tas_fits_term* terms, size_t num_terms, const int64_t* wl_off,
+                            size_t n_workloads, int32_t pods_col, const kueue_tas_delta* target_deltas,
+                            const int64_t* target_off, size_t n_targets, const int32_t* entry_targets,
+                            const int64_t* entry_target_off, int32_t* verdict);
 /* The same admission from the gathered block on the device (no host round
  * trip of the quads: the all-gather's receive block, rank 0's admission at 8
  * GPUs).  kueue_tas_admit_table first: for each of num_workloads compiled
@@ -526,6 +557,16 @@ int kueue_tas_host_last_assignments(kueue_tas_host* h, int32_t* buf, size_t cap,
 int kueue_tas_host_admit(kueue_tas_host* h, const int32_t* quads, size_t len, int32_t* admitted, size_t admitted_cap,
                          size_t* n_workloads, size_t* n_deltas);
 int kueue_tas_host_last_deltas(kueue_tas_host* h, kueue_tas_delta* buf, size_t cap);
+/* kueue_tas_host_admit for entries with preemption targets
+ * (kueue_tas_admit_targets): targets_json = {"workloads": [[usage records as
+ * in update_usage] per preemptable workload], "targets": [[entry id,
+ * [workload indices]], ...]} (an entry id at most once, and only ids present
+ * in the quads).  The usage records become delta records as
+ * kueue_tas_host_update_usage forms them (unknown domains skipped).
+ * admitted = (id, verdict 0 / 1 / 2) pairs; the host mirror and the delta list
+ * (kueue_tas_host_last_deltas) take the verdict-1 entries' usage only. */
+int kueue_tas_host_admit_targets(kueue_tas_host* h, const int32_t* quads, size_t len, const char* targets_json,
+                                 int32_t* admitted, size_t admitted_cap, size_t* n_workloads, size_t* n_deltas);
 int kueue_tas_host_apply_deltas(kueue_tas_host* h, const kueue_tas_delta* deltas, size_t n);
 /* admit from the all-gather's device block (kueue_tas_admit_block; block and
  * lens as gather_assignments leaves them): the same verdicts, admitted pairs

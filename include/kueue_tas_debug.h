@@ -172,6 +172,11 @@ int kueue_tas_host_last_admit_times(kueue_tas_host* h, double* ms3);
 // order-free admissions), candidates in total; -1 for the serial chain.
 int kueue_tas_last_admit_stats(kueue_tas_ctx* ctx, int64_t* out3);
 int kueue_tas_host_last_admit_stats(kueue_tas_host* h, int64_t* out3);
+// The last kueue_tas_admit / kueue_tas_admit_targets: [0] runs of target-free
+// entries that went through the pass, [1] admit_step_kernel launches, [2]
+// kernel launches in all (a call without targets: 1, 0, the pass's).
+int kueue_tas_last_admit_launches(kueue_tas_ctx* ctx, int64_t* out3);
+int kueue_tas_host_last_admit_launches(kueue_tas_host* h, int64_t* out3);
 
 #ifdef __cplusplus
 }

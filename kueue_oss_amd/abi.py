@@ -110,6 +110,14 @@ class EvalOut(c.Structure):  # kueue_tas_eval_out
     ]
 
 
+class FitsReq(c.Structure):  # kueue_tas_fits_req
+    _fields_ = [("leaf", c.c_int32), ("count", c.c_int32), ("term_begin", c.c_int32), ("num_terms", c.c_int32)]
+
+
+class FitsTerm(c.Structure):  # kueue_tas_fits_term
+    _fields_ = [("value", c.c_int64), ("col", c.c_int32), ("pad", c.c_int32)]
+
+
 class Config(c.Structure):  # kueue_tas_config
     _fields_ = [("list_cap", c.c_int32), ("max_batch", c.c_int32), ("device", c.c_int32), ("flags", c.c_int32)]
 
@@ -133,4 +141,13 @@ def bind_device_layer(lib):
     lib.kueue_tas_eval_batch.restype = c.c_int
     lib.kueue_tas_fetch_entries.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t]
     lib.kueue_tas_fetch_entries.restype = c.c_int
+    lib.kueue_tas_fits.argtypes = [c.c_void_p, P(FitsReq), c.c_size_t, P(FitsTerm), c.c_size_t, P(c.c_int32)]
+    lib.kueue_tas_fits.restype = c.c_int
+    lib.kueue_tas_admit.argtypes = [c.c_void_p, P(FitsReq), c.c_size_t, P(FitsTerm), c.c_size_t, P(c.c_int64),
+                                    c.c_size_t, c.c_int32, P(c.c_int32)]
+    lib.kueue_tas_admit.restype = c.c_int
+    lib.kueue_tas_admit_targets.argtypes = [c.c_void_p, P(FitsReq), c.c_size_t, P(FitsTerm), c.c_size_t, P(c.c_int64),
+                                            c.c_size_t, c.c_int32, P(Delta), P(c.c_int64), c.c_size_t, P(c.c_int32),
+                                            P(c.c_int64), P(c.c_int32)]
+    lib.kueue_tas_admit_targets.restype = c.c_int
     return lib

@@ -240,6 +240,10 @@ struct kueue_tas_ctx {
     const char* e = getenv("KTAS_ADMIT_PHASES");
     return e ? std::max(1, atoi(e)) : 6;
   }();
+  int admit_step_run = [] {  // kueue_tas_admit_targets: target-free runs shorter than this go through admit_step_kernel
+    const char* e = getenv("KTAS_ADMIT_STEP_RUN");
+    return e ? std::max(0, atoi(e)) : 2 * kAdmitWindow;
+  }();
   bool fused_top = false;     // rollup_top_kernel (KUEUE_TAS_CFG_FUSED_TOP)
   bool cat_fill = true;       // fill_pair_kernel's leaf categories (KUEUE_TAS_CFG_NO_CATEGORY_FILL clears it)
   bool labels16 = false;      // every staged label column's value ids < 2^16 (packed nodeSelector compare)
@@ -321,6 +325,7 @@ struct kueue_tas_ctx {
   DevBuf<uint64_t> d_leaf_tags;
   HostBuf<int32_t> h_admit;          // kueue_tas_admit's verdicts + its two diagnostics words (pinned D2H)
   int64_t admit_stats[3] = {-1, -1, -1};  // last kueue_tas_admit: window rounds, in-order candidates, candidates
+  int64_t admit_launches[3] = {0, 0, 0};  // last kueue_tas_admit(_targets): pass runs, step launches, kernel launches
   // kueue_tas_snapshot_splice: the gather's targets (the resident columns'
   // previous buffers after the swap, reused by the next splice) and its
   // pinned staging (leaf sources and joined rows)
@@ -1347,9 +1352,41 @@ static AdmitLayout admit_layout(size_t n, size_t num_terms, size_t n_wl, size_t 
 }
 static int admit_run(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const kueue_tas_fits_term* d_terms, size_t n,
                      size_t n_wl, int32_t pods_col, bool exact);
+// The arrays one pass reads and writes per record and per workload.
+struct AdmitView {
+  const kueue_tas_fits_req* reqs;  // [n]
+  const int32_t* recwl;            // [n] record -> workload
+  const int64_t* off;              // [n_wl + 1] workload -> records
+  int32_t* fit0;                   // [n_wl] phase-1 flags, 1 on entry
+  int32_t* out;                    // [n_wl + 3] verdicts + diagnostics
+  AdmitRec* recs;                  // [n]
+  int32_t* dep;                    // [n_wl]
+};
+static int admit_run_view(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const AdmitView& v,
+                          const kueue_tas_fits_term* d_terms, size_t n, size_t n_wl, int32_t pods_col, bool exact);
 
-int kueue_tas_admit(kueue_tas_ctx* c, const kueue_tas_fits_req* reqs, size_t n, const kueue_tas_fits_term* terms,
-                    size_t num_terms, const int64_t* wl_off, size_t n_wl, int32_t pods_col, int32_t* admitted) {
+// kueue_tas_admit_targets' extra arguments (null: kueue_tas_admit).
+struct AdmitTargets {
+  const kueue_tas_delta* deltas;  // the preemptable workloads' usage records
+  const int64_t* off;             // [T + 1] CSR into deltas
+  size_t T;
+  const int32_t* ids;             // the entries' target lists
+  const int64_t* eoff;            // [n_wl + 1] CSR into ids
+};
+// One stretch of the ordered entry list: a run of target-free entries for the
+// pass (admit_run_view), or entries for admit_step_kernel.
+struct AdmitSeg {
+  bool pass;
+  size_t a, b;
+};
+static int admit_targets_run(kueue_tas_ctx* c, const AdmitLayout& L, const kueue_tas_fits_req* reqs, size_t n,
+                             const kueue_tas_fits_term* terms, size_t num_terms, const int64_t* wl_off, size_t n_wl,
+                             int32_t pods_col, bool exact, const __int128* total, const AdmitTargets& tg,
+                             int32_t* verdict);
+
+static int admit_impl(kueue_tas_ctx* c, const kueue_tas_fits_req* reqs, size_t n, const kueue_tas_fits_term* terms,
+                      size_t num_terms, const int64_t* wl_off, size_t n_wl, int32_t pods_col, int32_t* admitted,
+                      const AdmitTargets* tg) {
   if (!c) return KUEUE_TAS_EINVAL;
   if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
   if (n_wl == 0) return KUEUE_TAS_OK;
@@ -1358,6 +1395,33 @@ int kueue_tas_admit(kueue_tas_ctx* c, const kueue_tas_fits_req* reqs, size_t n, 
   if (wl_off[0] != 0 || size_t(wl_off[n_wl]) != n) return fail(c, KUEUE_TAS_EINVAL, "workload offsets");
   for (size_t w = 0; w < n_wl; w++)
     if (wl_off[w + 1] < wl_off[w]) return fail(c, KUEUE_TAS_EINVAL, "workload offsets not monotone");
+  if (tg) {  // the target table and the entries' lists, before anything is enqueued
+    if (!tg->eoff || (tg->T && !tg->off)) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+    if (tg->T > size_t(INT32_MAX)) return fail(c, KUEUE_TAS_EINVAL, "too many targets");
+    if (tg->T && tg->off[0] != 0) return fail(c, KUEUE_TAS_EINVAL, "target offsets");
+    for (size_t t = 0; t < tg->T; t++)
+      if (tg->off[t + 1] < tg->off[t]) return fail(c, KUEUE_TAS_EINVAL, "target offsets not monotone");
+    const size_t nd = tg->T ? size_t(tg->off[tg->T]) : 0;
+    if (nd && !tg->deltas) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+    for (size_t j = 0; j < nd; j++) {
+      const kueue_tas_delta& x = tg->deltas[j];
+      if (x.leaf < -1 || x.leaf >= c->snap.N) return fail(c, KUEUE_TAS_EINVAL, "target record leaf out of range");
+      if (x.col < 0 || x.col >= c->snap.R) return fail(c, KUEUE_TAS_EINVAL, "target record column out of range");
+    }
+    if (tg->eoff[0] != 0) return fail(c, KUEUE_TAS_EINVAL, "entry target offsets");
+    for (size_t w = 0; w < n_wl; w++)
+      if (tg->eoff[w + 1] < tg->eoff[w]) return fail(c, KUEUE_TAS_EINVAL, "entry target offsets not monotone");
+    if (tg->eoff[n_wl] && !tg->ids) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+    std::vector<int64_t> last(tg->T, -1);  // the entry that listed the target last
+    for (size_t w = 0; w < n_wl; w++)
+      for (int64_t k = tg->eoff[w]; k < tg->eoff[w + 1]; k++) {
+        const int32_t t = tg->ids[k];
+        if (t < 0 || size_t(t) >= tg->T) return fail(c, KUEUE_TAS_EINVAL, "target id out of range");
+        if (last[size_t(t)] == int64_t(w)) return fail(c, KUEUE_TAS_EINVAL, "target listed twice by one entry");
+        last[size_t(t)] = int64_t(w);
+      }
+    if (tg->eoff[n_wl] == 0) tg = nullptr;  // no entry carries targets: kueue_tas_admit's pass as it is
+  }
   // per record on the host pool: the range checks, and for the monotone
   // shortcut (admit_fit0_kernel) the most usage this call can add per column
   // — the shortcut holds only for non-negative values and counts whose totals
@@ -1416,6 +1480,9 @@ int kueue_tas_admit(kueue_tas_ctx* c, const kueue_tas_fits_req* reqs, size_t n, 
   // one pinned upload: records, terms, workload offsets, record -> workload,
   // phase-1 flags (1 = fit) and the exact flag
   const AdmitLayout L = admit_layout(n, num_terms, n_wl, size_t(c->snap.N));
+  c->admit_launches[0] = 1;
+  c->admit_launches[1] = c->admit_launches[2] = 0;
+  if (tg) return admit_targets_run(c, L, reqs, n, terms, num_terms, wl_off, n_wl, pods_col, exact, total, *tg, admitted);
   HIPCHK(c, c->d_fits.ensure(L.end));
   HIPCHK(c, c->h_stage.ensure(L.up_bytes));
   uint8_t* h = c->h_stage.p;
@@ -1445,6 +1512,129 @@ int kueue_tas_admit(kueue_tas_ctx* c, const kueue_tas_fits_req* reqs, size_t n, 
   c->admit_stats[0] = c->admit_window ? c->h_admit.p[n_wl] : -1;
   c->admit_stats[1] = c->admit_window ? c->h_admit.p[n_wl + 1] : -1;
   c->admit_stats[2] = int64_t(n_wl);
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_admit(kueue_tas_ctx* c, const kueue_tas_fits_req* reqs, size_t n, const kueue_tas_fits_term* terms,
+                    size_t num_terms, const int64_t* wl_off, size_t n_wl, int32_t pods_col, int32_t* admitted) {
+  return admit_impl(c, reqs, n, terms, num_terms, wl_off, n_wl, pods_col, admitted, nullptr);
+}
+
+int kueue_tas_admit_targets(kueue_tas_ctx* c, const kueue_tas_fits_req* reqs, size_t n, const kueue_tas_fits_term* terms,
+                            size_t num_terms, const int64_t* wl_off, size_t n_wl, int32_t pods_col,
+                            const kueue_tas_delta* target_deltas, const int64_t* target_off, size_t n_targets,
+                            const int32_t* entry_targets, const int64_t* entry_target_off, int32_t* verdict) {
+  const AdmitTargets tg{target_deltas, target_off, n_targets, entry_targets, entry_target_off};
+  return admit_impl(c, reqs, n, terms, num_terms, wl_off, n_wl, pods_col, verdict, &tg);
+}
+
+// A validated call in which some entry carries targets.  The ordered list is
+// cut into runs of target-free entries, which go through the pass
+// (admit_run_view: inside a run the usage only grows, the preempted targets
+// staying subtracted), and the stretches between them — the target entries,
+// and target-free runs too short to pay for the pass's launches — which one
+// admit_step_kernel launch takes in order.  Everything is enqueued on the
+// context's stream; admit_restore_kernel puts the preempted targets' usage
+// back; one D2H brings the verdicts.
+static int admit_targets_run(kueue_tas_ctx* c, const AdmitLayout& L, const kueue_tas_fits_req* reqs, size_t n,
+                             const kueue_tas_fits_term* terms, size_t num_terms, const int64_t* wl_off, size_t n_wl,
+                             int32_t pods_col, bool exact, const __int128* total, const AdmitTargets& tg,
+                             int32_t* verdict) {
+  std::vector<AdmitSeg> segs;
+  const size_t min_run = size_t(std::max(c->admit_step_run, 1));
+  for (size_t w = 0; w < n_wl;) {
+    size_t e = w;
+    while (e < n_wl && tg.eoff[e + 1] == tg.eoff[e]) e++;  // [w, e): target-free
+    const bool pass = e - w >= min_run;
+    if (e == w) e = w + 1;  // a target entry
+    if (!pass && !segs.empty() && !segs.back().pass) segs.back().b = e;
+    else segs.push_back({pass, w, e});
+    w = e;
+  }
+  size_t n_pass = 0;
+  for (const AdmitSeg& sg : segs) n_pass += sg.pass ? 1 : 0;
+  // behind the pass's layout: the target table, the entries' lists, the runs'
+  // relative offsets (uploaded), the preempted bitmap
+  const size_t nd = size_t(tg.off[tg.T]), ne = size_t(tg.eoff[n_wl]), pwords = (tg.T + 31) / 32;
+  const size_t x_td = 0, x_toff = x_td + admit_al(nd * sizeof(kueue_tas_delta)), x_etg = x_toff + admit_al((tg.T + 1) * 8),
+               x_eoff = x_etg + admit_al(ne * 4), x_roff = x_eoff + admit_al((n_wl + 1) * 8),
+               x_up = x_roff + admit_al((n_wl + n_pass + 1) * 8), x_pre = x_up, x_end = x_pre + admit_al(pwords * 4);
+  HIPCHK(c, c->d_fits.ensure(L.end + x_end));
+  const size_t h_x = admit_al(L.up_bytes);
+  HIPCHK(c, c->h_stage.ensure(h_x + x_up));
+  uint8_t* h = c->h_stage.p;
+  if (n) memcpy(h, reqs, n * sizeof(kueue_tas_fits_req));
+  if (num_terms) memcpy(h + L.o_terms, terms, num_terms * sizeof(kueue_tas_fits_term));
+  memcpy(h + L.o_off, wl_off, (n_wl + 1) * 8);
+  int32_t* rec_wl = reinterpret_cast<int32_t*>(h + L.o_recwl);
+  int64_t* roff = reinterpret_cast<int64_t*>(h + h_x + x_roff);
+  std::vector<size_t> roff_at(segs.size(), 0);
+  size_t ro = 0;
+  for (size_t q = 0; q < segs.size(); q++) {  // record -> workload and the offsets, relative to the run
+    const AdmitSeg& sg = segs[q];
+    if (!sg.pass) continue;
+    roff_at[q] = ro;
+    for (size_t w = sg.a; w <= sg.b; w++) roff[ro++] = wl_off[w] - wl_off[sg.a];
+    for (size_t w = sg.a; w < sg.b; w++)
+      for (int64_t i = wl_off[w]; i < wl_off[w + 1]; i++) rec_wl[i] = int32_t(w - sg.a);
+  }
+  int32_t* fit0 = reinterpret_cast<int32_t*>(h + L.o_fit0);
+  for (size_t w = 0; w < n_wl; w++) fit0[w] = 1;
+  *reinterpret_cast<int32_t*>(h + L.o_exact) = exact ? 1 : 0;
+  for (int k = 0; k < KUEUE_TAS_MAX_COLS; k++)  // the call's total bounds every run's additions
+    reinterpret_cast<int64_t*>(h + L.o_total)[k] = exact ? 0 : int64_t(total[k]);
+  if (nd) memcpy(h + h_x + x_td, tg.deltas, nd * sizeof(kueue_tas_delta));
+  memcpy(h + h_x + x_toff, tg.off, (tg.T + 1) * 8);
+  memcpy(h + h_x + x_etg, tg.ids, ne * 4);
+  memcpy(h + h_x + x_eoff, tg.eoff, (n_wl + 1) * 8);
+  uint8_t* d = c->d_fits.p;
+  uint8_t* dx = d + L.end;
+  HIPCHK(c, hipMemcpyAsync(d, h, L.up_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dx, h + h_x, x_up, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(dx + x_pre, 0, admit_al(pwords * 4), c->stream));
+  const auto* d_reqs = reinterpret_cast<const kueue_tas_fits_req*>(d);
+  const auto* d_terms = reinterpret_cast<const kueue_tas_fits_term*>(d + L.o_terms);
+  const auto* d_td = reinterpret_cast<const kueue_tas_delta*>(dx + x_td);
+  const auto* d_toff = reinterpret_cast<const int64_t*>(dx + x_toff);
+  auto* d_pre = reinterpret_cast<uint32_t*>(dx + x_pre);
+  int32_t* d_out = reinterpret_cast<int32_t*>(d + L.o_out);
+  for (size_t q = 0; q < segs.size(); q++) {
+    const AdmitSeg& sg = segs[q];
+    if (sg.pass) {
+      const size_t r0 = size_t(wl_off[sg.a]);
+      const AdmitView v{d_reqs + r0,
+                        reinterpret_cast<const int32_t*>(d + L.o_recwl) + r0,
+                        reinterpret_cast<const int64_t*>(dx + x_roff) + roff_at[q],
+                        reinterpret_cast<int32_t*>(d + L.o_fit0) + sg.a,
+                        d_out + sg.a,
+                        reinterpret_cast<AdmitRec*>(d + L.o_recs) + r0,
+                        reinterpret_cast<int32_t*>(d + L.o_dep) + sg.a};
+      const int rc = admit_run_view(c, L, d, v, d_terms, size_t(wl_off[sg.b]) - r0, sg.b - sg.a, pods_col, exact);
+      if (rc) return rc;
+    } else {
+      hipLaunchKernelGGL(admit_step_kernel, dim3(1), dim3(1024), 0, c->stream, c->snap, c->d_usage.p,
+                         c->d_usage_present.p, d_reqs, d_terms, reinterpret_cast<const int64_t*>(d + L.o_off), int(sg.a),
+                         int(sg.b), pods_col, d_td, d_toff, reinterpret_cast<const int32_t*>(dx + x_etg),
+                         reinterpret_cast<const int64_t*>(dx + x_eoff), d_pre, d_out);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(admit_restore_kernel, dim3(unsigned(std::min<size_t>((tg.T + 3) / 4, 1024))), dim3(256), 0, c->stream,
+                     c->d_usage.p, c->snap.N, d_td, d_toff, int(tg.T), d_pre);
+  HIPCHK(c, hipGetLastError());
+  // the diagnostics words are the last run's; a run that ended short of the
+  // list's end left its own among the verdicts, which the later entries overwrote
+  if (!segs.back().pass) HIPCHK(c, hipMemsetAsync(d_out + n_wl, 0, 12, c->stream));
+  HIPCHK(c, c->h_admit.reserve(n_wl + 3));
+  HIPCHK(c, hipMemcpyAsync(c->h_admit.p, d_out, (n_wl + 3) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(verdict, c->h_admit.p, n_wl * 4);
+  c->admit_stats[0] = c->admit_window ? c->h_admit.p[n_wl] : -1;
+  c->admit_stats[1] = c->admit_window ? c->h_admit.p[n_wl + 1] : -1;
+  c->admit_stats[2] = int64_t(n_wl);
+  c->admit_launches[0] = int64_t(n_pass);
+  c->admit_launches[1] = int64_t(segs.size() - n_pass);
+  c->admit_launches[2] += int64_t(segs.size() - n_pass) + 1;  // + the passes' (admit_run_view)
   return KUEUE_TAS_OK;
 }
 
@@ -1571,6 +1761,8 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
   int64_t* ht = reinterpret_cast<int64_t*>(c->h_stage.p + 8);
   for (int k = 0; k < KUEUE_TAS_MAX_COLS; k++) ht[k] = exact ? 0 : tot64[k];
   HIPCHK(c, hipMemcpyAsync(d + L.o_total, ht, KUEUE_TAS_MAX_COLS * 8, hipMemcpyHostToDevice, c->stream));
+  c->admit_launches[0] = 1;
+  c->admit_launches[1] = c->admit_launches[2] = 0;
   const int rc = admit_run(c, L, d, c->d_adm_terms.p, nr, nwl, pods_col, exact);
   if (rc) return rc;
   // the admitted workloads' deltas on the device, in the host path's order
@@ -1616,6 +1808,19 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
 // the one-wave chain).  Verdicts at L.o_out.
 static int admit_run(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const kueue_tas_fits_term* d_terms, size_t n,
                      size_t n_wl, int32_t pods_col, bool exact) {
+  const AdmitView v{reinterpret_cast<const kueue_tas_fits_req*>(d), reinterpret_cast<const int32_t*>(d + L.o_recwl),
+                    reinterpret_cast<const int64_t*>(d + L.o_off), reinterpret_cast<int32_t*>(d + L.o_fit0),
+                    reinterpret_cast<int32_t*>(d + L.o_out), reinterpret_cast<AdmitRec*>(d + L.o_recs),
+                    reinterpret_cast<int32_t*>(d + L.o_dep)};
+  return admit_run_view(c, L, d, v, d_terms, n, n_wl, pods_col, exact);
+}
+
+// The pass over the n records / n_wl workloads `v` views: the whole call, or
+// one run of target-free entries of kueue_tas_admit_targets (record ->
+// workload and the offsets relative to the run).  The lists, the per-leaf
+// minima, the touched bitmap and the phase state are the layout's, reset here.
+static int admit_run_view(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const AdmitView& v,
+                          const kueue_tas_fits_term* d_terms, size_t n, size_t n_wl, int32_t pods_col, bool exact) {
   const size_t nwords = (size_t(c->snap.N) + 31) / 32;
   // the dynamic bitmaps share the workgroup's 64 KB of LDS with the kernel's
   // static arrays (the window kernel's fit / conflict flags and sweep scan)
@@ -1641,21 +1846,21 @@ static int admit_run(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const k
   const bool indep = c->admit_window && !exact && n > 0;
   if (indep) {
     HIPCHK(c, hipMemsetAsync(d + L.o_minc, 0x7f, size_t(c->snap.N) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(d + L.o_dep, 0, n_wl * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(v.dep, 0, n_wl * 4, c->stream));
   }
-  const auto* d_reqs = reinterpret_cast<const kueue_tas_fits_req*>(d);
+  const kueue_tas_fits_req* d_reqs = v.reqs;
   if (n) {
     hipLaunchKernelGGL(admit_fit0_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, c->stream, c->snap,
                        c->d_usage.p, c->d_usage_present.p, d_reqs, d_terms,
-                       reinterpret_cast<const int32_t*>(d + L.o_recwl), int(n), reinterpret_cast<const int64_t*>(d + L.o_total),
-                       reinterpret_cast<int32_t*>(d + L.o_fit0), reinterpret_cast<AdmitRec*>(d + L.o_recs),
+                       v.recwl, int(n), reinterpret_cast<const int64_t*>(d + L.o_total),
+                       v.fit0, v.recs,
                        reinterpret_cast<int32_t*>(d + L.o_exact));
     HIPCHK(c, hipGetLastError());
   }
   if (c->admit_window) {  // independent candidates in parallel, the rest windowed (one 1024-thread workgroup)
-    const auto* recwl = reinterpret_cast<const int32_t*>(d + L.o_recwl);
-    const auto* fit0d = reinterpret_cast<const int32_t*>(d + L.o_fit0);
-    auto* depd = reinterpret_cast<int32_t*>(d + L.o_dep);
+    const int32_t* recwl = v.recwl;
+    const int32_t* fit0d = v.fit0;
+    int32_t* depd = v.dep;
     if (indep) {
       const dim3 g(unsigned((n + 255) / 256));
       hipLaunchKernelGGL(admit_minc_kernel, g, dim3(256), 0, c->stream, d_reqs, recwl, int(n), fit0d, c->snap.N,
@@ -1667,8 +1872,8 @@ static int admit_run(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const k
       HIPCHK(c, hipGetLastError());
     }
     hipLaunchKernelGGL(admit_todo_kernel, dim3(1), dim3(1024), 0, c->stream, int(n_wl), fit0d, depd, indep ? 0 : 1,
-                       reinterpret_cast<int32_t*>(d + L.o_out), reinterpret_cast<int32_t*>(d + L.o_todo),
-                       reinterpret_cast<const int64_t*>(d + L.o_off), reinterpret_cast<int64_t*>(d + L.o_todor));
+                       v.out, reinterpret_cast<int32_t*>(d + L.o_todo),
+                       v.off, reinterpret_cast<int64_t*>(d + L.o_todor));
     HIPCHK(c, hipGetLastError());
     // the window kernel in phases: each stops at a rejection sweep, which the
     // grid runs (a wave per remaining candidate) before the next phase
@@ -1681,28 +1886,35 @@ static int admit_run(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const k
     for (int ph = 0; ph < phases; ph++) {
       if (ph > 0) {
         hipLaunchKernelGGL(admit_sweep_kernel, dim3(1024), dim3(256), 0, c->stream, c->snap, c->d_usage.p,
-                           c->d_usage_present.p, d_reqs, d_terms, reinterpret_cast<const AdmitRec*>(d + L.o_recs), fit0d,
-                           reinterpret_cast<const uint32_t*>(d + L.o_bits), reinterpret_cast<int32_t*>(d + L.o_out), todo,
+                           c->d_usage_present.p, d_reqs, d_terms, v.recs, fit0d,
+                           reinterpret_cast<const uint32_t*>(d + L.o_bits), v.out, todo,
                            todor, st);
         hipLaunchKernelGGL(admit_compact_kernel, dim3(1), dim3(1024), 0, c->stream, todo, todor, st);
       }
       hipLaunchKernelGGL(admit_window_kernel, dim3(1), dim3(64 * kAdmitWindow),
                          lds_chain ? 2 * nwords * 4 : lds_bits ? nwords * 4 : 0, c->stream, c->snap, c->d_usage.p,
-                         c->d_usage_present.p, d_reqs, d_terms, reinterpret_cast<const AdmitRec*>(d + L.o_recs),
-                         reinterpret_cast<const int64_t*>(d + L.o_off), int(n_wl), pods_col,
-                         reinterpret_cast<const int32_t*>(d + L.o_fit0), reinterpret_cast<const int32_t*>(d + L.o_exact),
+                         c->d_usage_present.p, d_reqs, d_terms, v.recs,
+                         v.off, int(n_wl), pods_col,
+                         v.fit0, reinterpret_cast<const int32_t*>(d + L.o_exact),
                          reinterpret_cast<uint32_t*>(d + L.o_bits), lds_chain ? 2 : lds_bits ? 1 : 0,
-                         reinterpret_cast<int32_t*>(d + L.o_out), todo, todor, st, ph + 1 < phases ? 1 : 0);
+                         v.out, todo, todor, st, ph + 1 < phases ? 1 : 0);
       HIPCHK(c, hipGetLastError());
     }
   } else {  // one wave down the chain
     hipLaunchKernelGGL(admit_kernel, dim3(1), dim3(64), lds_bits ? nwords * 4 : 0, c->stream, c->snap, c->d_usage.p,
-                       c->d_usage_present.p, d_reqs, d_terms, reinterpret_cast<const AdmitRec*>(d + L.o_recs),
-                       reinterpret_cast<const int64_t*>(d + L.o_off), int(n_wl),
-                       pods_col, reinterpret_cast<const int32_t*>(d + L.o_fit0), reinterpret_cast<const int32_t*>(d + L.o_exact),
-                       reinterpret_cast<uint32_t*>(d + L.o_bits), lds_bits ? 1 : 0, reinterpret_cast<int32_t*>(d + L.o_out));
+                       c->d_usage_present.p, d_reqs, d_terms, v.recs,
+                       v.off, int(n_wl),
+                       pods_col, v.fit0, reinterpret_cast<const int32_t*>(d + L.o_exact),
+                       reinterpret_cast<uint32_t*>(d + L.o_bits), lds_bits ? 1 : 0, v.out);
   }
   HIPCHK(c, hipGetLastError());
+  c->admit_launches[2] += (n ? 1 : 0) + (c->admit_window ? (indep ? 3 : 0) + 1 + 3 * c->admit_grid_sweeps - 2 : 1);
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_last_admit_launches(kueue_tas_ctx* c, int64_t* out3) {
+  if (!c || !out3) return KUEUE_TAS_EINVAL;
+  memcpy(out3, c->admit_launches, sizeof c->admit_launches);
   return KUEUE_TAS_OK;
 }
 

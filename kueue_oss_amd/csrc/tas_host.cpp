@@ -4982,10 +4982,28 @@ int kueue_tas_host_last_assignments(kueue_tas_host* h, int32_t* buf, size_t cap,
 // ComputeTASNetUsage builds them, flavorassigner.go:94-130: per assigned
 // domain, the PodSet's single-pod requests and the domain's count).  The
 // device applies the usage (kueue_tas_admit); the host mirror follows.
-int kueue_tas_host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, int32_t* admitted, size_t admitted_cap,
-                         size_t* n_workloads, size_t* n_deltas) {
+// With targets_json (kueue_tas_host_admit_targets): the preemptable
+// workloads' usage becomes delta records as update_usage forms them, the
+// entries' target lists follow the ascending ids, and the device decides the
+// three-valued verdicts (kueue_tas_admit_targets).
+static int host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, const char* targets_json, int32_t* admitted,
+                      size_t admitted_cap, size_t* n_workloads, size_t* n_deltas) {
   if (!h || !h->snap || !h->err.empty() || (len && !recs) || len % 4 || !n_workloads) return KUEUE_TAS_EINVAL;
   try {
+    std::vector<std::vector<FlavorSnapshot::DomainUsage>> tgUsage;  // per preemptable workload
+    std::vector<std::pair<int32_t, std::vector<int32_t>>> tgLists;  // (entry id, workload indices)
+    if (targets_json) {
+      const kjson::Node doc = kjson::parse(targets_json);
+      for (auto& w : doc["workloads"].items) tgUsage.push_back(FlavorSnapshot::parse_usage(w));
+      for (auto& e : doc["targets"].items) {
+        if (e.items.size() != 2) throw std::runtime_error("admit: targets entry is not [id, [workloads]]");
+        std::vector<int32_t> l;
+        for (auto& t : e.items[1].items) l.push_back(int32_t(t.i64()));
+        tgLists.push_back({int32_t(e.items[0].i64()), std::move(l)});
+      }
+      // a column for every resource the targets' usage names (the next upload reloads then)
+      for (auto& us : tgUsage) h->snap->ensure_columns_for_usage(us);
+    }
     // workloads in ascending id (the gathered quads of every rank; a
     // workload's quads are contiguous per rank), capacity checked first:
     // nothing is admitted when the caller's buffer is short
@@ -5144,8 +5162,48 @@ int kueue_tas_host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, int
     const auto pods = s.colByName.find("pods");
     const int32_t pods_col = pods == s.colByName.end() ? -1 : pods->second;
     const double t1 = now_ms();
-    rc = kueue_tas_admit(s.ctx, fr.data(), fr.size(), terms.data(), terms.size(), off.data(), ids.size(), pods_col,
-                         adm.data());
+    if (targets_json) {
+      // RemoveUsage's records per target, as update_usage forms them
+      // (single x count per resource and pods:count, in resource-name order;
+      // a domain that is no leaf of the snapshot is skipped)
+      std::vector<kueue_tas_delta> td;
+      std::vector<int64_t> toff{0};
+      for (auto& us : tgUsage) {
+        for (auto& u : us) {
+          const int32_t leaf = s.leafById.find(u.id);
+          if (leaf < 0) continue;
+          Requests tot;
+          for (auto& kv : u.single) tot[kv.first] = mul64(kv.second, u.count);
+          tot["pods"] = add64(tot["pods"], u.count);
+          for (auto& kv : tot) {
+            const auto col = s.colByName.find(kv.first);
+            if (col == s.colByName.end()) throw std::runtime_error("admit: target resource without a column");
+            td.push_back({leaf, col->second, kv.second});
+          }
+        }
+        toff.push_back(int64_t(td.size()));
+      }
+      std::vector<int32_t> pos(W, -1);  // id -> position in the ascending list
+      for (size_t k = 0; k < ids.size(); k++) pos[size_t(ids[k])] = int32_t(k);
+      std::vector<const std::vector<int32_t>*> per(ids.size(), nullptr);
+      for (auto& e : tgLists) {
+        if (e.first < 0 || size_t(e.first) >= W || pos[size_t(e.first)] < 0)
+          throw std::runtime_error("admit: targets for an entry that is not in the batch");
+        if (per[size_t(pos[size_t(e.first)])]) throw std::runtime_error("admit: targets given twice for one entry");
+        per[size_t(pos[size_t(e.first)])] = &e.second;
+      }
+      std::vector<int32_t> etg;
+      std::vector<int64_t> eoff{0};
+      for (size_t k = 0; k < ids.size(); k++) {
+        if (per[k]) etg.insert(etg.end(), per[k]->begin(), per[k]->end());
+        eoff.push_back(int64_t(etg.size()));
+      }
+      rc = kueue_tas_admit_targets(s.ctx, fr.data(), fr.size(), terms.data(), terms.size(), off.data(), ids.size(),
+                                   pods_col, td.data(), toff.data(), tgUsage.size(), etg.data(), eoff.data(), adm.data());
+    } else {
+      rc = kueue_tas_admit(s.ctx, fr.data(), fr.size(), terms.data(), terms.size(), off.data(), ids.size(), pods_col,
+                           adm.data());
+    }
     if (rc) {
       h->err = std::string("admit: ") + kueue_tas_last_error(s.ctx);
       return rc;
@@ -5157,7 +5215,7 @@ int kueue_tas_host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, int
     for (size_t k = 0; k < ids.size(); k++) {
       admitted[2 * k] = ids[k];
       admitted[2 * k + 1] = adm[k];
-      if (!adm[k]) continue;
+      if (adm[k] != 1) continue;  // (2: skipped, overlapping preemption targets)
       for (int64_t i = off[k]; i < off[k + 1]; i++) {
         const kueue_tas_fits_req& r = fr[size_t(i)];
         for (int q = 0; q < r.num_terms; q++) {
@@ -5177,6 +5235,17 @@ int kueue_tas_host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, int
     h->err = e.what();
     return KUEUE_TAS_EINVAL;
   }
+}
+
+int kueue_tas_host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, int32_t* admitted, size_t admitted_cap,
+                         size_t* n_workloads, size_t* n_deltas) {
+  return host_admit(h, recs, len, nullptr, admitted, admitted_cap, n_workloads, n_deltas);
+}
+
+int kueue_tas_host_admit_targets(kueue_tas_host* h, const int32_t* quads, size_t len, const char* targets_json,
+                                 int32_t* admitted, size_t admitted_cap, size_t* n_workloads, size_t* n_deltas) {
+  if (!targets_json) return KUEUE_TAS_EINVAL;
+  return host_admit(h, quads, len, targets_json, admitted, admitted_cap, n_workloads, n_deltas);
 }
 
 int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t row_words, const int64_t* lens,
@@ -5264,6 +5333,11 @@ int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t r
 int kueue_tas_host_last_admit_stats(kueue_tas_host* h, int64_t* out3) {
   if (!h || !h->snap || !h->snap->ctx || !out3) return KUEUE_TAS_EINVAL;
   return kueue_tas_last_admit_stats(h->snap->ctx, out3);
+}
+
+int kueue_tas_host_last_admit_launches(kueue_tas_host* h, int64_t* out3) {
+  if (!h || !h->snap || !h->snap->ctx || !out3) return KUEUE_TAS_EINVAL;
+  return kueue_tas_last_admit_launches(h->snap->ctx, out3);
 }
 
 int kueue_tas_host_last_admit_times(kueue_tas_host* h, double* ms3) {

@@ -6630,6 +6630,139 @@ __global__ __launch_bounds__(1024) void admit_compact_kernel(int32_t* todo, int6
   }
 }
 
+// ---- admission of entries with preemption targets (kueue_tas_admit_targets) ----
+// processEntry for an entry that carries targets (scheduler.go:419-435,
+// fits() :621-629): skipped when a target is already preempted in this cycle;
+// else Fits under SimulateWorkloadRemoval(preempted + its targets)
+// (snapshot.go:67-84 -> removeTASUsage, tas_flavor_snapshot.go:281-293), and
+// when it fits its targets join the preempted set and its usage is added.
+// The preempted targets stay physically subtracted from tas_usage for the
+// rest of the call (admit_restore_kernel adds them back at its end), so the
+// usage every later entry is checked against is the reference's, and inside a
+// run of target-free entries it only grows: the host hands such runs to the
+// pass above, and the entries between them — in order, exact CountIn, no
+// phase-1 shortcut — to this one workgroup.  Per entry w of [w_begin, w_end):
+//  1. any of its targets in the `preempted` bitmap: verdict 2, nothing changes;
+//  2. its targets' delta records leave tas_usage (wrapping 64-bit atomics:
+//     records of different targets may share a (leaf, column); the key is
+//     created like Requests.Sub does; a record with leaf -1 is skipped);
+//  3. drained counters and a barrier, then every record's Fits over the
+//     workgroup's threads (L1-bypassing loads, as the window kernel's);
+//  4. fits: verdict 1, the targets marked preempted, the entry's usage added
+//     (updateTASUsage); else verdict 0 and the targets' records put back.
+// An entry without targets takes steps 3 and 4 only.
+__global__ __launch_bounds__(1024) void admit_step_kernel(
+    DevSnap s, int64_t* tas_usage, uint32_t* usage_present, const kueue_tas_fits_req* reqs,
+    const kueue_tas_fits_term* terms, const int64_t* wl_off, int w_begin, int w_end, int pods_col,
+    const kueue_tas_delta* tdeltas, const int64_t* toff, const int32_t* etg, const int64_t* etoff, uint32_t* preempted,
+    int32_t* verdict) {
+  __shared__ int32_t sh_step[2];  // [0] a target already preempted, [1] a record that does not fit
+  const int lane = lane_id(), wave = int(threadIdx.x) >> 6, nwaves = int(blockDim.x) >> 6;
+  if (threadIdx.x == 0) sh_step[0] = sh_step[1] = 0;
+  __syncthreads();
+  for (int w = w_begin; w < w_end; w++) {  // block-uniform
+    const int64_t t0 = etoff[w], t1 = etoff[w + 1];
+    const int64_t r0 = wl_off[w], r1 = wl_off[w + 1];
+    if (t1 > t0) {
+      bool hit = false;
+      for (int64_t k = t0 + threadIdx.x; k < t1; k += blockDim.x) {
+        const int32_t t = etg[k];
+        hit |= (load_l2(preempted + (t >> 5)) >> (t & 31)) & 1u;
+      }
+      if (hit) sh_step[0] = 1;  // (the same value from every writer)
+      __syncthreads();
+      const bool overlap = sh_step[0] != 0;
+      __syncthreads();
+      if (overlap) {  // "overlapping preemption targets": skipped
+        if (threadIdx.x == 0) {
+          verdict[w] = 2;
+          sh_step[0] = 0;
+        }
+        __syncthreads();
+        continue;
+      }
+      for (int64_t k = t0 + wave; k < t1; k += nwaves) {  // RemoveUsage: a wave per target
+        const int32_t t = etg[k];
+        for (int64_t j = toff[t] + lane; j < toff[t + 1]; j += kWave) {
+          const kueue_tas_delta x = tdeltas[j];
+          if (x.leaf < 0) continue;
+          atomicAdd(reinterpret_cast<unsigned long long*>(tas_usage + int64_t(x.col) * s.N + x.leaf),
+                    (unsigned long long)(0ull - uint64_t(x.delta)));
+          atomicOr(usage_present + x.leaf, 1u << x.col);
+        }
+      }
+      admit_drain();  // the removal performed at L2 before any wave's loads
+      __syncthreads();
+    }
+    bool bad = false;
+    for (int64_t i = r0 + threadIdx.x; i < r1 && !bad; i += blockDim.x)
+      bad = !admit_record_fits(s, tas_usage, usage_present, reqs[i], terms);
+    if (bad) sh_step[1] = 1;
+    __syncthreads();
+    const bool fits = sh_step[1] == 0;
+    __syncthreads();
+    if (fits) {
+      for (int64_t k = t0 + threadIdx.x; k < t1; k += blockDim.x) {
+        const int32_t t = etg[k];
+        atomicOr(preempted + (t >> 5), 1u << (t & 31));
+      }
+      for (int64_t i = r0 + threadIdx.x; i < r1; i += blockDim.x) {  // AddUsage (a fitting entry's leaves are valid)
+        const kueue_tas_fits_req r = reqs[i];
+        uint32_t bits = 0;
+        for (int q = 0; q < r.num_terms; q++) {
+          const kueue_tas_fits_term t = terms[r.term_begin + q];
+          if (t.col >= 0) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(tas_usage + int64_t(t.col) * s.N + r.leaf),
+                      (unsigned long long)(uint64_t(t.value) * uint64_t(int64_t(r.count))));
+            bits |= 1u << t.col;
+          }
+        }
+        if (pods_col >= 0) {
+          atomicAdd(reinterpret_cast<unsigned long long*>(tas_usage + int64_t(pods_col) * s.N + r.leaf),
+                    (unsigned long long)int64_t(r.count));
+          bits |= 1u << pods_col;
+        }
+        atomicOr(usage_present + r.leaf, bits);
+      }
+    } else {
+      for (int64_t k = t0 + wave; k < t1; k += nwaves) {  // the simulated removal reverted
+        const int32_t t = etg[k];
+        for (int64_t j = toff[t] + lane; j < toff[t + 1]; j += kWave) {
+          const kueue_tas_delta x = tdeltas[j];
+          if (x.leaf < 0) continue;
+          atomicAdd(reinterpret_cast<unsigned long long*>(tas_usage + int64_t(x.col) * s.N + x.leaf),
+                    (unsigned long long)uint64_t(x.delta));
+        }
+      }
+    }
+    if (threadIdx.x == 0) {
+      verdict[w] = fits ? 1 : 0;
+      sh_step[1] = 0;
+    }
+    admit_drain();  // this entry's atomics performed at L2 before the next entry's loads
+    __syncthreads();
+  }
+}
+
+// The end of a call with targets: every preempted target's records go back
+// into tas_usage (the reference reverts the simulated removal after each
+// check; the targets' usage stays in the snapshot).  A wave per target.
+__global__ __launch_bounds__(256) void admit_restore_kernel(int64_t* tas_usage, int N, const kueue_tas_delta* tdeltas,
+                                                            const int64_t* toff, int n_targets,
+                                                            const uint32_t* preempted) {
+  const int lane = lane_id();
+  const int waves = int(gridDim.x * (blockDim.x >> 6));
+  for (int t = int(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); t < n_targets; t += waves) {
+    if (!((preempted[t >> 5] >> (t & 31)) & 1u)) continue;
+    for (int64_t j = toff[t] + lane; j < toff[t + 1]; j += kWave) {
+      const kueue_tas_delta x = tdeltas[j];
+      if (x.leaf < 0) continue;
+      atomicAdd(reinterpret_cast<unsigned long long*>(tas_usage + int64_t(x.col) * N + x.leaf),
+                (unsigned long long)uint64_t(x.delta));
+    }
+  }
+}
+
 
 // ---- admission from the gathered device block (kueue_tas_admit_block) ----
 // The all-gather leaves every rank's assignments in one device block, row r

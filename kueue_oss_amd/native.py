@@ -70,7 +70,8 @@ EXPORTED_SYMBOLS = [
     "kueue_tas_snapshot_usage_mark", "kueue_tas_snapshot_usage_changes", "kueue_tas_snapshot_apply_deltas_mirrored",
     "kueue_tas_host_partial_admission_search", "kueue_tas_last_host_trace", "kueue_tas_merge_reruns",
     "kueue_tas_select_groups", "kueue_tas_admit_table", "kueue_tas_admit_block", "kueue_tas_copy_to_host",
-    "kueue_tas_host_admit_block",
+    "kueue_tas_host_admit_block", "kueue_tas_admit_targets", "kueue_tas_host_admit_targets",
+    "kueue_tas_last_admit_launches", "kueue_tas_host_last_admit_launches",
 ]
 
 # the Makefile's SRC_HASH inputs, in order
@@ -224,6 +225,10 @@ def _bind(lib):
                                                     c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t),
                                                     c.POINTER(c.c_void_p)]
     lib.kueue_tas_host_compile_workload.restype = c.c_int
+    lib.kueue_tas_host_admit_targets.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_char_p, c.c_void_p, c.c_size_t,
+                                                 c.POINTER(c.c_size_t), c.POINTER(c.c_size_t)]
+    lib.kueue_tas_host_admit_targets.restype = c.c_int
+    lib.kueue_tas_host_last_admit_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
 
 
 def resource_quantity_string(name: str, value: int, lib=None) -> str:
@@ -546,6 +551,44 @@ class TASFlavorSnapshot:
         if self._lib.kueue_tas_host_last_deltas(self._h, deltas.ctypes.data, deltas.size):
             raise RuntimeError(self._err())
         return adm[: nw.value], deltas
+
+    def admit_with_targets(self, quads, workloads, targets):
+        """admit() for a cycle whose entries carry preemption targets
+        (processEntry, scheduler.go:419-435; kueue_tas_host_admit_targets):
+        ``workloads`` the preemptable workloads as usage-record lists (their
+        usage is in the snapshot), ``targets`` {entry id: [workload indices]}
+        or [(entry id, [workload indices])].  Returns (pairs (id, verdict)
+        [n, 2] with verdict 0 rejected / 1 admitted / 2 skipped for overlapping
+        targets, deltas of the admitted entries)."""
+        import numpy as np
+        q = np.ascontiguousarray(quads, dtype=np.int32)
+        items = targets.items() if hasattr(targets, "items") else targets
+        doc = json.dumps({"workloads": workloads,
+                          "targets": [[int(i), [int(t) for t in ts]] for i, ts in items]}).encode()
+        heads = int(np.count_nonzero(q[1::4] < 0)) if q.size else 0
+        adm = np.zeros((heads, 2), dtype=np.int32)
+        nw = ctypes.c_size_t()
+        nd = ctypes.c_size_t()
+        rc = self._lib.kueue_tas_host_admit_targets(self._h, q.ctypes.data, q.size, doc, adm.ctypes.data, adm.size,
+                                                    ctypes.byref(nw), ctypes.byref(nd))
+        if rc == -5 and nw.value > heads:  # workloads without a header quad: size by the library's count
+            adm = np.zeros((nw.value, 2), dtype=np.int32)
+            rc = self._lib.kueue_tas_host_admit_targets(self._h, q.ctypes.data, q.size, doc, adm.ctypes.data, adm.size,
+                                                        ctypes.byref(nw), ctypes.byref(nd))
+        if rc:
+            raise RuntimeError(self._err())
+        deltas = np.zeros(nd.value, dtype=DELTA_DTYPE)
+        if self._lib.kueue_tas_host_last_deltas(self._h, deltas.ctypes.data, deltas.size):
+            raise RuntimeError(self._err())
+        return adm[: nw.value], deltas
+
+    def last_admit_launches(self):
+        """The last admit / admit_with_targets: (target-free runs through the pass,
+        step-kernel launches, kernel launches in all)."""
+        out = (ctypes.c_int64 * 3)()
+        if self._lib.kueue_tas_host_last_admit_launches(self._h, out):
+            raise RuntimeError(self._err())
+        return tuple(out)
 
     def admit_block(self, block, lens, row_words=None):
         """admit() from the all-gather's receive block on the device
