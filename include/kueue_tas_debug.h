@@ -97,7 +97,13 @@ int64_t kueue_tas_last_alias_fills(kueue_tas_ctx* ctx);
 #define KUEUE_TAS_PATH_RAGGED_PAIR 32768u       /* fill_pair_kernel on ragged leaf parents (128-leaf slots, segmented scans) */
 #define KUEUE_TAS_PATH_CATEGORY 65536u          /* fill_pair_kernel's single-run chunks classify leaf categories (CAT) */
 #define KUEUE_TAS_PATH_LFC_FILL 131072u         /* the fast-LFC chunk tables accumulated by the fill (no lfc_hist_kernel) */
+#define KUEUE_TAS_PATH_FUSED_TOP 262144u        /* rollup_top_kernel ran (KUEUE_TAS_CFG_FUSED_TOP and a level above the
+                                                   fused one with a fan-out of 8 or more): not rollup_level_* / rollup_tail */
 uint32_t kueue_tas_last_fill_paths(kueue_tas_ctx* ctx);
+/* kueue_tas_eval_batch / _ptrs calls on ctx so far: what a reader of the last
+ * batch's state (kueue_tas_last_counters, the entry views) compares to know
+ * that no later batch replaced it. */
+uint64_t kueue_tas_eval_generation(kueue_tas_ctx* ctx);
 /* Stage events: on (default), every stage of kueue_tas_last_stage_times is
  * timed; off, only the fill bracket is (the other events are pure
  * instrumentation; the ones that order the streams are always recorded). */
@@ -163,6 +169,21 @@ int kueue_tas_host_last_stats(kueue_tas_host* h, int64_t* stats8);
 /* kueue_tas_host_last_stats followed by [8] the fill rows whose sliceState
  * aliases state (kueue_tas_last_alias_fills summed); copies min(n, 9). */
 int kueue_tas_host_last_stats_ext(kueue_tas_host* h, int64_t* out, int32_t n);
+/* kueue_tas_last_counters for compiled workload `workload` (its index in the
+ * last kueue_tas_host_run: the shard's when one is set) — the phase-1
+ * counters of the PodSet group the run evaluated last for it, through the
+ * workload-to-request mapping the balanced path uses.  Valid after
+ * kueue_tas_host_run / run_compiled for a workload whose last group was in
+ * the run's last device batch and, there, in its last device chunk
+ * (max_batch): in practice workloads of one PodSet group, no more than
+ * max_batch of them.  KUEUE_TAS_EINVAL when the workload had no request in
+ * that batch (an early failure of the prelude, an earlier pass), when
+ * TASBalancedPlacement re-evaluated requests after it, or when anything else
+ * evaluated a batch on the handle's context since the run (a find, a search,
+ * a direct kueue_tas_eval_batch: kueue_tas_eval_generation moved); otherwise
+ * kueue_tas_last_counters' result (EINVAL for a request outside the last
+ * chunk).  So another batch's rows are never returned for the run's index. */
+int kueue_tas_host_last_counters(kueue_tas_host* h, size_t workload, int32_t* out, size_t cap);
 /* Host wall time of the last kueue_tas_host_admit (ms): [0] record
  * preparation, [1] kueue_tas_admit (uploads, admit_kernel, result copy),
  * [2] delta list. */

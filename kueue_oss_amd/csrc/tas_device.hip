@@ -409,6 +409,7 @@ struct kueue_tas_ctx {
   int64_t last_stats[4] = {0, 0, 0, 0};  // fill evals, leaf-partial evals, fill launches, staged columns
   int64_t last_alias_fills = 0;          // fill rows whose sliceState aliases state (FillEvalParams::ss_alias)
   uint32_t fill_paths = 0;               // KUEUE_TAS_PATH_* bits of the last kueue_tas_eval_batch
+  uint64_t eval_gen = 0;                 // kueue_tas_eval_batch calls so far (kueue_tas_eval_generation)
   // phase-1 counters of the last device chunk (kueue_tas_last_counters):
   // requests [chunk_base, chunk_base + chunk_rep.size()), their class counter rows
   size_t chunk_base = 0;
@@ -3102,6 +3103,7 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
   const bool fused_top = c->fused_top && nfill > 0 && upper >= 0 && s.level_size[upper] > 0 && top_parents <= 4096 &&
                          s.level_size[upper + 1] / s.level_size[upper] >= 8;
   if (fused_top) {  // every upper level and the level maxima in one launch
+    c->fill_paths |= KUEUE_TAS_PATH_FUSED_TOP;
     b.level_max = nbf > 0 ? reinterpret_cast<int32_t*>(ds + o_top) : nullptr;
     const int per_block = 4 * kParentsPerWave;
     dim3 grid((s.level_size[upper] + per_block - 1) / per_block, unsigned(nfill));
@@ -3378,6 +3380,7 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* c, const kueue_tas_eval_req* const*
   c->last_alias_fills = 0;
   for (auto& v : c->host_ms) v = 0;
   c->fill_paths = 0;
+  c->eval_gen++;
   const size_t chunk = size_t(c->max_batch);
   std::vector<int64_t> off;
   entry_offsets[0] = 0;
@@ -3567,6 +3570,7 @@ int kueue_tas_last_host_times(kueue_tas_ctx* c, double* ms, int n) {  // copies 
 }
 
 uint32_t kueue_tas_last_fill_paths(kueue_tas_ctx* c) { return c ? c->fill_paths : 0u; }
+uint64_t kueue_tas_eval_generation(kueue_tas_ctx* c) { return c ? c->eval_gen : 0u; }
 
 int64_t kueue_tas_last_alias_fills(kueue_tas_ctx* c) { return c ? c->last_alias_fills : 0; }
 

@@ -2692,6 +2692,11 @@ struct Evaluator {
   std::vector<std::pair<size_t, GroupEval*>> p0_batch, p0_early;
   std::vector<size_t> used;  // results set per workload in this run
   std::string reasonBuf;
+  // the run's last device batch (request i belongs to workload (*ctr_bt)[i].first);
+  // null when its counters are gone (kueue_tas_host_last_counters)
+  const std::vector<std::pair<size_t, GroupEval*>>* ctr_bt = nullptr;
+  kueue_tas_ctx* ctr_ctx = nullptr;  // the context and its kueue_tas_eval_generation right after that batch
+  uint64_t ctr_gen = 0;
 
   // Results are updated in place (member order = first set in this run), so
   // repeated runs reuse the strings' and vectors' storage.
@@ -2941,10 +2946,12 @@ struct Evaluator {
   std::vector<kueue_tas_eval_req> balReq;
   std::vector<kueue_tas_eval_out> balOuts;
   std::vector<int64_t> balOffs;
+  bool balReran = false;  // the last balanced_pass ran a device batch of its own
   int balanced_pass(const std::vector<const kueue_tas_eval_req*>& rq, const std::vector<int32_t>& tt,
                     const std::vector<kueue_tas_affinity_req>* af, const std::vector<int32_t>* afv,
                     const std::vector<std::pair<size_t, GroupEval*>>& bt, const int32_t** ent_view) {
     const size_t n = bt.size();
+    balReran = false;
     balOut.assign(n, BalancedOut{});
     std::vector<size_t> idx;
     for (size_t i = 0; i < n; i++)
@@ -2971,6 +2978,7 @@ struct Evaluator {
     const size_t last0 = n > 0 ? (n - 1) / chunk * chunk : 0;
     std::vector<size_t> again, here;
     for (size_t i : idx) (i >= last0 ? here : again).push_back(i);
+    balReran = !again.empty();
     auto place = [&](size_t i, size_t slot) -> int {  // the counters of request `slot` of the last batch -> balOut[i]
       balCtr.resize(std::max<size_t>(5 * total, 1));
       int rc = kueue_tas_last_counters(s.ctx, slot, balCtr.data(), balCtr.size());
@@ -3050,6 +3058,7 @@ struct Evaluator {
     double t_prep = t_start;  // start of the current pass's preparation
     results->resize(wls.size());
     used.assign(wls.size(), 0);
+    ctr_bt = nullptr;
     if (!precompiled) {
       // grouping (FindTopologyAssignmentsForFlavor :528-541) and the
       // findTopologyAssignment prelude (:804-897) per workload, over the host
@@ -3172,6 +3181,9 @@ struct Evaluator {
       stats[5] += kueue_tas_last_alias_fills(snap->ctx);
       rc = balanced_pass(*rq, *tt, af, afv, *bt, &ent_view);  // after the diagnostics: it may run a batch
       if (rc) return rc;
+      ctr_bt = balReran ? nullptr : bt;  // re-run: the context now holds the balanced re-evaluation
+      ctr_ctx = snap->ctx;
+      ctr_gen = kueue_tas_eval_generation(snap->ctx);
       const double t_decode = now_ms();
       host_ms[1] += t_decode - t_call;
       counts[0]++;
@@ -4846,6 +4858,16 @@ int kueue_tas_host_last_stage_times(kueue_tas_host* h, float* ms, int n) {
 int kueue_tas_host_last_eval_ticks(kueue_tas_host* h, int32_t* ticks, size_t n) {
   if (!h || !h->snap) return KUEUE_TAS_EINVAL;
   return kueue_tas_last_eval_ticks(h->snap->ctx, ticks, n);
+}
+
+int kueue_tas_host_last_counters(kueue_tas_host* h, size_t workload, int32_t* out, size_t cap) {
+  if (!h || !h->snap || !h->ev || !out) return KUEUE_TAS_EINVAL;
+  const auto* bt = h->ev->ctr_bt;
+  if (!bt || h->ev->ctr_ctx != h->snap->ctx || h->ev->ctr_gen != kueue_tas_eval_generation(h->snap->ctx))
+    return KUEUE_TAS_EINVAL;  // gone, or a later batch on the context replaced the run's rows
+  for (size_t i = 0; i < bt->size(); i++)
+    if ((*bt)[i].first == workload) return kueue_tas_last_counters(h->snap->ctx, i, out, cap);
+  return KUEUE_TAS_EINVAL;
 }
 
 int kueue_tas_host_last_eval_profile(kueue_tas_host* h, int32_t* ticks, size_t n) {

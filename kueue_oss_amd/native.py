@@ -71,7 +71,8 @@ EXPORTED_SYMBOLS = [
     "kueue_tas_host_partial_admission_search", "kueue_tas_last_host_trace", "kueue_tas_merge_reruns",
     "kueue_tas_select_groups", "kueue_tas_admit_table", "kueue_tas_admit_block", "kueue_tas_copy_to_host",
     "kueue_tas_host_admit_block", "kueue_tas_admit_targets", "kueue_tas_host_admit_targets",
-    "kueue_tas_last_admit_launches", "kueue_tas_host_last_admit_launches",
+    "kueue_tas_last_admit_launches", "kueue_tas_host_last_admit_launches", "kueue_tas_host_last_counters",
+    "kueue_tas_eval_generation",
 ]
 
 # the Makefile's SRC_HASH inputs, in order
@@ -229,6 +230,12 @@ def _bind(lib):
                                                  c.POINTER(c.c_size_t), c.POINTER(c.c_size_t)]
     lib.kueue_tas_host_admit_targets.restype = c.c_int
     lib.kueue_tas_host_last_admit_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
+    lib.kueue_tas_host_last_counters.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]
+    lib.kueue_tas_host_last_counters.restype = c.c_int
+    lib.kueue_tas_last_counters.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t]
+    lib.kueue_tas_last_counters.restype = c.c_int
+    lib.kueue_tas_last_fill_paths.argtypes = [c.c_void_p]
+    lib.kueue_tas_last_fill_paths.restype = c.c_uint32
 
 
 def resource_quantity_string(name: str, value: int, lib=None) -> str:
@@ -499,6 +506,18 @@ class TASFlavorSnapshot:
         t, p2 = ctypes.c_int64(), ctypes.c_int64()
         self._lib.kueue_tas_device_bytes(self.device_ctx(), ctypes.byref(t), ctypes.byref(p2))
         return t.value, p2.value
+
+    def last_counters(self, workload: int, num_domains: int):
+        """Phase-1 counters of compiled workload ``workload`` in the last
+        run_compiled (kueue_tas_host_last_counters): int32 array [5, S] of
+        state, sliceState, stateWithLeader, sliceStateWithLeader, leaderState
+        over the S = ``num_domains`` domains of every level from the top."""
+        import numpy as np
+        out = np.empty(5 * num_domains, dtype=np.int32)
+        rc = self._lib.kueue_tas_host_last_counters(self._h, workload, out.ctypes.data, out.size)
+        if rc:
+            raise RuntimeError(f"kueue_tas_host_last_counters failed ({rc}) for workload {workload}")
+        return out.reshape(5, num_domains)
 
     def last_results(self) -> list:
         """Results of the last run_compiled, one result list per compiled workload."""

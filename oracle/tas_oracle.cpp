@@ -1152,6 +1152,31 @@ class Snapshot {
     return place_slices_balanced(cur, sliceCount, st.leaderCount, st.sliceSize, bestThreshold, out);
   }
 
+  // Phase-1 counters as kueue_tas_last_counters lays them out: out[f * S + g],
+  // f = state, sliceState, stateWithLeader, sliceStateWithLeader, leaderState,
+  // g over the levels from the top, each level in levels_in_order()'s order.
+  std::vector<int32_t>* phase1Counters = nullptr;
+  std::string phase1Params;  // the prelude's slice parameters of that request (JSON)
+  static constexpr const char* kPhase1Stop = "<phase 1 only>";
+  std::vector<std::vector<Domain*>> levels_in_order() const {  // lexicographic levelValues (slices.Compare)
+    std::vector<std::vector<Domain*>> out;
+    for (auto& lvl : domainsPerLevel) {
+      std::vector<Domain*> v;
+      for (auto& kv : lvl) v.push_back(kv.second);
+      std::sort(v.begin(), v.end(), [](Domain* a, Domain* b) { return compare_values(a->levelValues, b->levelValues) < 0; });
+      out.push_back(std::move(v));
+    }
+    return out;
+  }
+  void dump_counters(std::vector<int32_t>& out) const {
+    const auto lv = levels_in_order();
+    for (int f = 0; f < 5; f++)
+      for (auto& v : lv)
+        for (Domain* d : v)
+          out.push_back(f == 0 ? d->state : f == 1 ? d->sliceState : f == 2 ? d->stateWithLeader
+                        : f == 3 ? d->sliceStateWithLeader : d->leaderState);
+  }
+
   // findTopologyAssignment (:804-999)
   std::string find_topology_assignment(const PodSetRequest& workers, const PodSetRequest* leader,
                                        std::map<std::string, Requests>& assumed, bool simulateEmpty,
@@ -1207,6 +1232,21 @@ class Snapshot {
     }
 
     fill_in_counts(rq, st);
+    if (phase1Counters) {  // tas_oracle_counters: stop before phase 2 rewrites the counters in place
+      if (phase1Counters->empty()) {
+        dump_counters(*phase1Counters);
+        phase1Params = "{\"sliceSize\":" + std::to_string(st.sliceSize) + ",\"sliceLevelIdx\":" +
+                       std::to_string(st.sliceLevelIdx) + ",\"leader\":" + (st.leaderCount > 0 ? "true" : "false") +
+                       ",\"sliceSizeAtLevel\":{";
+        bool first = true;
+        for (auto& kv : st.sliceSizeAtLevel) {
+          phase1Params += std::string(first ? "" : ",") + "\"" + std::to_string(kv.first) + "\":" + std::to_string(kv.second);
+          first = false;
+        }
+        phase1Params += "}}";
+      }
+      return kPhase1Stop;
+    }
 
     int fitLevelIdx = 0;
     std::vector<Domain*> cur;
@@ -2077,6 +2117,127 @@ int tas_oracle_session(const char* snapshot_json, const char* ops_json, char** o
   }
   *out_json = dup_out(out);
   return 0;
+}
+
+// Phase-1 counters (fill_in_counts + fill_in_counts_helper, stopped before any
+// phase-2 step) of every workload's first PodSet group, each against the
+// snapshot as built: {"levels": [[levelValues...] per domain] per level,
+// "results": [{"counters": [5 * S ints, kueue_tas_last_counters' layout] or
+// null when the prelude fails before phase 1, "reason": that failure,
+// "params": the prelude's sliceSize, sliceLevelIdx, leader, sliceSizeAtLevel}]}.
+int tas_oracle_counters(const char* snapshot_json, const char* workloads_json, int simulate_empty, char** out_json) {
+  using namespace oracle;
+  try {
+    ojson::Value c = ojson::parse(snapshot_json);
+    ojson::Value w = ojson::parse(workloads_json);
+    auto snap = build_snapshot(c);
+    std::string out = "{\"levels\":[";
+    bool firstL = true;
+    for (auto& lvl : snap->levels_in_order()) {
+      out += firstL ? "[" : ",[";
+      firstL = false;
+      for (size_t i = 0; i < lvl.size(); i++) {
+        out += i ? ",[" : "[";
+        // a hostname leaf keeps its levelValues only (:160-195); they end in its id
+        for (size_t k = 0; k < lvl[i]->levelValues.size(); k++) {
+          if (k) out += ",";
+          ojson::quote(out, lvl[i]->levelValues[k]);
+        }
+        out += "]";
+      }
+      out += "]";
+    }
+    out += "],\"results\":[";
+    bool first = true;
+    for (auto& wl : w.at("workloads").a) {
+      std::vector<int32_t> ctr;
+      snap->phase1Counters = &ctr;
+      auto rs = snap->find_topology_assignments_for_flavor(parse_podsets(wl), simulate_empty != 0);
+      snap->phase1Counters = nullptr;
+      out += first ? "{\"counters\":" : ",{\"counters\":";
+      first = false;
+      if (ctr.empty()) {
+        out += "null,\"reason\":";
+        ojson::quote(out, rs.empty() ? std::string() : rs[0].reason);
+      } else {
+        out += "[";
+        for (size_t i = 0; i < ctr.size(); i++) out += (i ? "," : "") + std::to_string(ctr[i]);
+        out += "],\"reason\":\"\",\"params\":" + snap->phase1Params;
+      }
+      out += "}";
+    }
+    out += "]}";
+    *out_json = dup_out(out);
+    return 0;
+  } catch (const std::exception& e) {
+    std::string out = "{\"error\":";
+    ojson::quote(out, e.what());
+    out += "}";
+    *out_json = dup_out(out);
+    return -1;
+  }
+}
+
+// The reference's unit-test entry points, called as its tests call them:
+//   {"op": "countIn", "requests": {...}, "capacity": {...}}
+//       -> {"count", "limitingResource"} (count_in_with_limiting)
+//   {"op": "sortedDomains", "withLeader": bool, "unconstrained": bool,
+//    "profileMixed": bool (default true), "domains": [{"id", "levelValues",
+//    and any of the five counters (default 0)}]}
+//       -> {"order": [ids]} (sorted_domains_with_leader / sorted_domains on
+//          bare domains of a one-level snapshot)
+int tas_oracle_unit(const char* op_json, char** out_json) {
+  using namespace oracle;
+  try {
+    ojson::Value op = ojson::parse(op_json);
+    const std::string kind = op.at("op").as_str();
+    std::string out;
+    if (kind == "countIn") {
+      auto r = count_in_with_limiting(parse_requests(op.at("requests")), parse_requests(op.at("capacity")));
+      out = "{\"count\":" + std::to_string(r.first) + ",\"limitingResource\":";
+      ojson::quote(out, r.second);
+      out += "}";
+    } else if (kind == "sortedDomains") {
+      Snapshot snap({"block"}, {});
+      if (auto pm = op.get("profileMixed")) snap.gates.profileMixed = pm->as_bool();
+      std::deque<Domain> store;
+      std::vector<Domain*> ds;
+      auto field = [](const ojson::Value& d, const char* k) {
+        auto v = d.get(k);
+        return v && !v->is_null() ? int32_t(v->as_int()) : int32_t(0);
+      };
+      for (auto& d : op.at("domains").a) {
+        store.emplace_back();
+        Domain& x = store.back();
+        x.id = d.at("id").as_str();
+        for (auto& v : d.at("levelValues").a) x.levelValues.push_back(v.as_str());
+        x.state = field(d, "state");
+        x.sliceState = field(d, "sliceState");
+        x.stateWithLeader = field(d, "stateWithLeader");
+        x.sliceStateWithLeader = field(d, "sliceStateWithLeader");
+        x.leaderState = field(d, "leaderState");
+        ds.push_back(&x);
+      }
+      const bool unc = op.at("unconstrained").as_bool();
+      auto sorted = op.at("withLeader").as_bool() ? snap.sorted_domains_with_leader(ds, unc) : snap.sorted_domains(ds, unc);
+      out = "{\"order\":[";
+      for (size_t i = 0; i < sorted.size(); i++) {
+        if (i) out += ",";
+        ojson::quote(out, sorted[i]->id);
+      }
+      out += "]}";
+    } else {
+      throw std::runtime_error("unknown op " + kind);
+    }
+    *out_json = dup_out(out);
+    return 0;
+  } catch (const std::exception& e) {
+    std::string out = "{\"error\":";
+    ojson::quote(out, e.what());
+    out += "}";
+    *out_json = dup_out(out);
+    return -1;
+  }
 }
 
 void tas_oracle_free(char* p) { free(p); }

@@ -33,6 +33,10 @@ def load():
     lib.tas_oracle_session.restype = ctypes.c_int
     lib.tas_oracle_encoding.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     lib.tas_oracle_encoding.restype = ctypes.c_int
+    lib.tas_oracle_counters.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
+    lib.tas_oracle_counters.restype = ctypes.c_int
+    lib.tas_oracle_unit.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+    lib.tas_oracle_unit.restype = ctypes.c_int
     lib.tas_oracle_free.argtypes = [ctypes.c_void_p]
     _lib = lib
     return lib
@@ -67,6 +71,37 @@ def eval_workloads(snapshot_case: dict, workloads: list, threads: int = 1, emit:
     if rc != 0:
         raise RuntimeError(doc.get("error"))
     return doc["results"], secs.value
+
+
+def counters(snapshot_case: dict, workloads: list, simulate_empty: bool = False) -> dict:
+    """Phase-1 counters (fillInCounts + fillInCountsHelper, before any phase-2
+    step) of every workload's first PodSet group against the snapshot:
+    {"levels": per level the domains' levelValues in lexicographic order,
+    "results": [{"counters": 5 * S ints laid out [field][level-major domain]
+    (state, sliceState, stateWithLeader, sliceStateWithLeader, leaderState) or
+    None when the prelude fails before phase 1, "reason": that failure}]}."""
+    lib = load()
+    out = ctypes.c_void_p()
+    rc = lib.tas_oracle_counters(json.dumps(snapshot_case).encode(), json.dumps({"workloads": workloads}).encode(),
+                                 1 if simulate_empty else 0, ctypes.byref(out))
+    doc = _take(lib, out)
+    if rc != 0:
+        raise RuntimeError(doc.get("error"))
+    return doc
+
+
+def unit(op: dict) -> dict:
+    """One of the reference's unit-level entry points: {"op": "countIn",
+    "requests", "capacity"} -> {"count", "limitingResource"};
+    {"op": "sortedDomains", "withLeader", "unconstrained", "domains"} ->
+    {"order": [ids]}."""
+    lib = load()
+    out = ctypes.c_void_p()
+    rc = lib.tas_oracle_unit(json.dumps(op).encode(), ctypes.byref(out))
+    doc = _take(lib, out)
+    if rc != 0:
+        raise RuntimeError(doc.get("error"))
+    return doc
 
 
 def session(snapshot_case: dict, ops: list) -> list:

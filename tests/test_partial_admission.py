@@ -7,10 +7,13 @@ which walks sort.Search one probe at a time on an oracle snapshot.  The
 device path evaluates sort.Search's decision tree speculatively, a batch of
 levels per launch; the answer and the probe count must be the reference's
 for any fits predicate (the tests use small batches too, so a search spans
-many launches).  The reference's tests exercise the reducer only through the
-whole scheduler (scheduler_test.go partial admission cases, quota-driven), so
-no TAS-level golden exists: parity rests on the find goldens that pin every
-evaluation and on the restatement below."""
+many launches).  The reference's tests exercise the reducer over TAS only
+through the whole scheduler (scheduler_test.go partial admission cases,
+quota-driven), so no TAS-level golden exists; the search arithmetic itself
+has the nine vectors of TestSearch (podset_reducer_test.go:26-150), pinned in
+tests/golden/reducer_search.json and run through the TAS fit by
+tests/test_reference_vectors.py.  Beyond those, parity rests on the find
+goldens that pin every evaluation and on the restatement below."""
 import random
 
 import pytest
