@@ -54,10 +54,15 @@ int64_t kueue_tas_last_fill_profile(kueue_tas_ctx* ctx, int32_t* out, size_t n);
  * validation pass, [7] the records + class-hash pass.  Copies min(n, 8). */
 int kueue_tas_last_host_times(kueue_tas_ctx* ctx, double* ms, int n);
 /* Host timeline of the last device chunk (ms since its start) at 20 fixed
- * points: validate, staging layout, records, table copies, class merge, class
- * members, chunk order, member lists, classes done, buffers, fill records,
- * upload, fill launches, roll-up launches, LFC branch, select launch, D2H
- * enqueued, synchronized, offsets (tools/probe_host.py --trace). */
+ * points, each after the eval_chunk stage it names (tas_device.hip): [0] start,
+ * [1] validate_requests, [2] layout_stage, [3] compile_requests, [4]
+ * copy_tables, [5] merge_classes, [6] assign_reps_and_slots, [7] and [8] inside
+ * order_fill_chunks (class order, member lists), [9] order_fill_chunks, [10]
+ * size_device_buffers + ensure_entry_regions, [11] build_fill_records, [12]
+ * inside upload_and_describe (uploads), [13] enqueue_fill, [14]
+ * enqueue_stats_branch + enqueue_rollup, [15] enqueue_fast_lfc, [16]
+ * enqueue_bestfit_select (before [15]), [17] enqueue_results_d2h, [18]
+ * sync_and_check, [19] claim_entry_regions (tools/probe_trace.py). */
 int kueue_tas_last_host_trace(kueue_tas_ctx* ctx, double* ms, int n);
 /* Device chunks re-run with the exact class merge after the speculative
  * merge's verification failed (a 64-bit class hash collision, or

@@ -219,6 +219,42 @@ void compute_magic(uint64_t d, DevTerm* t, MagicCache& cache) {
   t->pow2 = c.pow2;
 }
 
+// Environment knobs, read once per context at creation (kueue_tas_ctx_create;
+// a KUEUE_TAS_CFG_* flag that overrides one writes into the same struct).
+struct Knobs {
+  int admit_grid_sweeps = 6;  // KTAS_ADMIT_PHASES: window-kernel phases (rejection sweeps over the grid between them); 1: in-kernel
+  int admit_step_run = 2 * kAdmitWindow;  // KTAS_ADMIT_STEP_RUN: kueue_tas_admit_targets: target-free runs shorter than this go
+                                          // through admit_step_kernel
+  int64_t phase2_budget = int64_t(4096) << 20;  // KTAS_PHASE2_BUDGET: bytes of select lists + overlays + tags per slot group
+                                                // (tests: a small budget, many groups)
+  bool force_scratch_rerun = false;  // KTAS_SCRATCH_TEST_RERUN (set): tests: every chunk re-runs once
+  int64_t lcap_test_cap = 0;         // KTAS_SCRATCH_TEST_CAP: tests: bounded lists capped lower (overflows re-run unbounded)
+  bool scratch_bounded = true;       // KTAS_SCRATCH_FULL=1 clears it: every slot's lists sized for the widest level
+  bool lfc_in_fill = false;    // KTAS_LFC_IN_FILL=1: fast-LFC chunk tables from the pair fill (no lfc_hist_kernel);
+                               // off by default: it lengthens the fill on the main chain
+                               // by more than it saves the side stream
+  bool emit_after_bf = false;  // KTAS_EMIT_MAIN=1: lfc_emit on the main stream after the BestFit select
+  int32_t exp_flags = 0;       // KTAS_EXP_FLAGS: diagnostics only (tools/probe_select.py experiments)
+
+  static Knobs from_env() {
+    Knobs k;
+    auto on = [](const char* name) {
+      const char* e = getenv(name);
+      return e && atoi(e) != 0;
+    };
+    if (const char* e = getenv("KTAS_ADMIT_PHASES")) k.admit_grid_sweeps = std::max(1, atoi(e));
+    if (const char* e = getenv("KTAS_ADMIT_STEP_RUN")) k.admit_step_run = std::max(0, atoi(e));
+    if (const char* e = getenv("KTAS_PHASE2_BUDGET")) k.phase2_budget = std::max<int64_t>(atoll(e), 1);
+    k.force_scratch_rerun = getenv("KTAS_SCRATCH_TEST_RERUN") != nullptr;
+    if (const char* e = getenv("KTAS_SCRATCH_TEST_CAP")) k.lcap_test_cap = std::max<int64_t>(atoll(e), 1);
+    k.scratch_bounded = !on("KTAS_SCRATCH_FULL");
+    k.lfc_in_fill = on("KTAS_LFC_IN_FILL");
+    k.emit_after_bf = on("KTAS_EMIT_MAIN");
+    if (const char* e = getenv("KTAS_EXP_FLAGS")) k.exp_flags = int32_t(atoi(e));
+    return k;
+  }
+};
+
 }  // namespace
 
 struct kueue_tas_ctx {
@@ -236,15 +272,8 @@ struct kueue_tas_ctx {
   bool inline_stats = true;   // ExclusionStats counted in the fill (KUEUE_TAS_CFG_SPLIT_STATS: fill_exclusion_kernel)
   bool pair_fill = true;      // fill_pair_kernel for single-run chunks (KUEUE_TAS_CFG_NO_PAIR_FILL clears it)
   bool admit_window = true;   // admit_window_kernel (KUEUE_TAS_CFG_SERIAL_ADMIT: the one-wave chain)
-  int admit_grid_sweeps = [] {  // window-kernel phases (rejection sweeps over the grid between them); 1: in-kernel
-    const char* e = getenv("KTAS_ADMIT_PHASES");
-    return e ? std::max(1, atoi(e)) : 6;
-  }();
-  int admit_step_run = [] {  // kueue_tas_admit_targets: target-free runs shorter than this go through admit_step_kernel
-    const char* e = getenv("KTAS_ADMIT_STEP_RUN");
-    return e ? std::max(0, atoi(e)) : 2 * kAdmitWindow;
-  }();
-  bool fused_top = false;     // rollup_top_kernel (KUEUE_TAS_CFG_FUSED_TOP)
+  Knobs knobs;                // the KTAS_* environment knobs (Knobs::from_env at creation)
+  bool fused_top = false;    // rollup_top_kernel (KUEUE_TAS_CFG_FUSED_TOP)
   bool cat_fill = true;       // fill_pair_kernel's leaf categories (KUEUE_TAS_CFG_NO_CATEGORY_FILL clears it)
   bool labels16 = false;      // every staged label column's value ids < 2^16 (packed nodeSelector compare)
   int64_t n_loads = 0, n_splices = 0;  // kueue_tas_snapshot_load / _splice calls that succeeded (lifetime)
@@ -370,38 +399,13 @@ struct kueue_tas_ctx {
   std::vector<int32_t> sel_groups;      // last batch: BestFit-side slot groups (select launches), bounds
   bool scratch_full = false;            // this chunk re-runs with unbounded select lists (an eval overflowed)
   int64_t scratch_reruns = 0;           // chunks re-run so
-  int64_t phase2_budget = [] {          // bytes of select lists + overlays + tags per slot group
-    const char* e = getenv("KTAS_PHASE2_BUDGET");  // (tests: a small budget, many groups)
-    return e ? std::max<int64_t>(atoll(e), 1) : int64_t(4096) << 20;
-  }();
-  bool force_scratch_rerun = getenv("KTAS_SCRATCH_TEST_RERUN") != nullptr;  // tests: every chunk re-runs once
-  int64_t lcap_test_cap = [] {          // tests: bounded lists capped lower (overflows re-run unbounded)
-    const char* e = getenv("KTAS_SCRATCH_TEST_CAP");
-    return e ? std::max<int64_t>(atoll(e), 1) : int64_t(0);
-  }();
-  bool scratch_bounded = [] {           // KTAS_SCRATCH_FULL=1: every slot's lists sized for the widest level
-    const char* e = getenv("KTAS_SCRATCH_FULL");
-    return !(e && atoi(e) != 0);
-  }();
   DevBufLink* dev_bufs = nullptr;       // every DevBuf member (kueue_tas_device_bytes)
   bool exact_merge = false;  // the next chunk merges the parts' classes with exact compares (after a collision)
   int64_t merge_reruns = 0;  // chunks re-run after a class hash collision
   size_t lfc_half = 0;        // LFC chunk-table entries per half of d_lfc_ch / d_lfc_ovs
   bool lfc_dirty[2] = {true, true};  // a half not known to be zero
   int lfc_parity = 0;         // the half the next batch with fast-LFC evals uses
-  bool lfc_in_fill = [] {     // KTAS_LFC_IN_FILL=1: fast-LFC chunk tables from the pair fill (no lfc_hist_kernel);
-    const char* e = getenv("KTAS_LFC_IN_FILL");  // off by default: it lengthens the fill on the main chain
-    return e && atoi(e) != 0;                     // by more than it saves the side stream
-  }();
   bool collide_test = false; // KUEUE_TAS_CFG_CLASS_COLLIDE
-  bool emit_after_bf = [] {    // KTAS_EMIT_MAIN=1: lfc_emit on the main stream after the BestFit select
-    const char* e = getenv("KTAS_EMIT_MAIN");
-    return e && atoi(e) != 0;
-  }();
-  int32_t exp_flags = [] {     // diagnostics only (tools/probe_select.py experiments)
-    const char* e = getenv("KTAS_EXP_FLAGS");
-    return e ? int32_t(atoi(e)) : 0;
-  }();
 
   double trace[24] = {};  // the last chunk's host timeline (wall ms at fixed points, kueue_tas_last_host_trace)
   double host_ms[8] = {};  // last batch host time: compile, classes, enqueue, wait, pack+D2H, copy-out, [6] of compile:
@@ -461,6 +465,7 @@ kueue_tas_ctx* kueue_tas_ctx_create(const kueue_tas_config* cfg) {
   auto* c = new kueue_tas_ctx();
   g_devbuf_chain = nullptr;
   c->dev_bufs = chain;
+  c->knobs = Knobs::from_env();
   if (cfg) {
     c->device = cfg->device;
     c->inline_stats = (cfg->flags & KUEUE_TAS_CFG_INLINE_STATS) != 0 || (cfg->flags & KUEUE_TAS_CFG_SPLIT_STATS) == 0;
@@ -469,7 +474,7 @@ kueue_tas_ctx* kueue_tas_ctx_create(const kueue_tas_config* cfg) {
     c->fused_top = (cfg->flags & KUEUE_TAS_CFG_FUSED_TOP) != 0;
     c->cat_fill = (cfg->flags & KUEUE_TAS_CFG_NO_CATEGORY_FILL) == 0;
     c->collide_test = (cfg->flags & KUEUE_TAS_CFG_CLASS_COLLIDE) != 0;
-    if (cfg->flags & KUEUE_TAS_CFG_LFC_IN_FILL) c->lfc_in_fill = true;
+    if (cfg->flags & KUEUE_TAS_CFG_LFC_IN_FILL) c->knobs.lfc_in_fill = true;
     if (cfg->list_cap > 0) {
       int lc = 64;
       while (lc < cfg->list_cap && lc < 1024) lc <<= 1;
@@ -1542,7 +1547,7 @@ static int admit_targets_run(kueue_tas_ctx* c, const AdmitLayout& L, const kueue
                              int32_t pods_col, bool exact, const __int128* total, const AdmitTargets& tg,
                              int32_t* verdict) {
   std::vector<AdmitSeg> segs;
-  const size_t min_run = size_t(std::max(c->admit_step_run, 1));
+  const size_t min_run = size_t(std::max(c->knobs.admit_step_run, 1));
   for (size_t w = 0; w < n_wl;) {
     size_t e = w;
     while (e < n_wl && tg.eoff[e + 1] == tg.eoff[e]) e++;  // [w, e): target-free
@@ -1883,7 +1888,7 @@ static int admit_run_view(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, co
     int32_t* st = reinterpret_cast<int32_t*>(d + L.o_state);
     int32_t* todo = reinterpret_cast<int32_t*>(d + L.o_todo);
     int64_t* todor = reinterpret_cast<int64_t*>(d + L.o_todor);
-    const int phases = c->admit_grid_sweeps;
+    const int phases = c->knobs.admit_grid_sweeps;
     for (int ph = 0; ph < phases; ph++) {
       if (ph > 0) {
         hipLaunchKernelGGL(admit_sweep_kernel, dim3(1024), dim3(256), 0, c->stream, c->snap, c->d_usage.p,
@@ -1909,7 +1914,7 @@ static int admit_run_view(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, co
                        reinterpret_cast<uint32_t*>(d + L.o_bits), lds_bits ? 1 : 0, v.out);
   }
   HIPCHK(c, hipGetLastError());
-  c->admit_launches[2] += (n ? 1 : 0) + (c->admit_window ? (indep ? 3 : 0) + 1 + 3 * c->admit_grid_sweeps - 2 : 1);
+  c->admit_launches[2] += (n ? 1 : 0) + (c->admit_window ? (indep ? 3 : 0) + 1 + 3 * c->knobs.admit_grid_sweeps - 2 : 1);
   return KUEUE_TAS_OK;
 }
 
@@ -1934,7 +1939,7 @@ int kueue_tas_last_admit_stats(kueue_tas_ctx* c, int64_t* out3) {
 // only while pods remain, :1236-1321); twice that, as the unbounded capacity
 // is twice the widest level.  Unconstrained, multi-layer and replacement
 // walks keep the unbounded lists.  An overflow still re-runs the chunk
-// unbounded (eval_chunk returns 2), so the bound costs memory, never results.
+// unbounded (eval_chunk returns ChunkRerun), so the bound costs memory, never results.
 static int64_t scratch_bound(const kueue_tas_ctx* c, const DevSnap& s, const DevEval& ev, int64_t full) {
   if (ev.flags & (KUEUE_TAS_F_UNCONSTRAINED | KUEUE_TAS_F_MULTILAYER | KUEUE_TAS_F_DOMAIN)) return full;
   const int r = ev.requested_level;
@@ -1948,46 +1953,238 @@ static int64_t scratch_bound(const kueue_tas_ctx* c, const DevSnap& s, const Dev
                                                                                c->level_maxfan[size_t(l - 1)]));
   }
   int64_t lc = std::min(full, 2 * std::max(top, below) + 64);
-  if (c->lcap_test_cap) lc = std::min(lc, std::max(c->lcap_test_cap, std::min(full, 2 * top + 64)));  // (descent lists only)
+  if (c->knobs.lcap_test_cap) lc = std::min(lc, std::max(c->knobs.lcap_test_cap, std::min(full, 2 * top + 64)));  // (descent lists only)
   return lc;
 }
 
 
-static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, size_t n, const int32_t* taint_table,
-                      size_t taint_table_len, int32_t num_taints, const kueue_tas_assumed* assumed, size_t num_assumed,
-                      const kueue_tas_affinity_req* aff, size_t num_aff, const int32_t* aff_vals, size_t num_aff_vals,
-                      kueue_tas_eval_out* out, int64_t* offsets, int32_t* taint_counts, int32_t* res_counts,
-                      float* ms, float* stage_ms) {
-  const int32_t entry_cap = c->entry_cap;
+// ---- eval_chunk: one device chunk of kueue_tas_eval_batch_ptrs, as a sequence
+// of stages over an explicit plan.  The host stages decide the ChunkPlan, the
+// enqueue stages consume it; the per-class and per-request vectors the stages
+// share stay on the context (kept between batches). ----
+
+// The caller's arrays: filled once per batch, narrowed per chunk.
+struct ChunkArgs {
+  const kueue_tas_eval_req* const* reqs;
+  size_t n;
+  const int32_t* taint_table;
+  size_t taint_table_len;
+  int32_t num_taints;
+  const kueue_tas_assumed* assumed;
+  size_t num_assumed;
+  const kueue_tas_affinity_req* aff;
+  size_t num_aff;
+  const int32_t* aff_vals;
+  size_t num_aff_vals;
+  kueue_tas_eval_out* out;
+  int64_t* offsets;
+  int32_t* taint_counts;
+  int32_t* res_counts;
+  float* ms;
+  float* stage_ms;
+};
+
+// Byte offsets of the staging arena's segments (h_stage and d_stage alike).
+struct ArenaOffsets {
+  size_t evals, terms, taint, assumed, aff, affv;
+  size_t fill, fchunks, pairs, rep, frun, slot, lrep, fast, leafsel, pidx, bf;
+  size_t moff, mem;  // class members in fill order (CSR)
+  size_t top;        // rollup_top_kernel's level maxima (INT32_MIN) and per-class arrival counters (0)
+  size_t sel;        // BestFit-side select slots' buffers
+  size_t fpos;       // last: the per-position fill records, uploaded up to the batch's nfill
+};
+
+struct ChunkPlan {
+  ArenaOffsets o{};
+  size_t nterms = 0;
+  int maxt = 1;  // the widest request's term count
+  // fill positions (classes), rep/member pairs, fast-LFC table slots, fast-LFC evals, BestFit-side evals, fill
+  // chunks, leaf-level select evals, signature runs, single-run chunks (the first nsingle of nfchunks)
+  int nfill = 0, npairs = 0, nslots = 0, nfast = 0, nbf = 0, nfchunks = 0, nleafsel = 0, nruns = 0, nsingle = 0;
+  uint32_t umask = 0;  // snapshot columns any request reads
+  int ucols = 0;
+  int nstat_all = 0;       // ExclusionStats fields per class
+  bool lds_stats = false;  // the staged fill counts them in LDS
+  int64_t full_lcap = 0;   // a list of any level's domains, twice
+  int nchunks = 0;         // LFC leaf chunks
+  int nblk = 0;            // leaf partials per eval (one per 64-leaf wave)
+  int lfc_cur = 0;         // the half of the LFC chunk tables this chunk uses
+  size_t res_bytes = 0, res_off_stats = 0, stats_len = 0;  // d_res / h_res: out[n] | stats
+};
+
+// What the fill-path decision yields (enqueue_fill)
+struct FillLaunch {
+  bool staged_fill = false, pair = false, ragged_pair = false, gl = false, ts = false, cat = false, wide = false;
+  unsigned pgx = 0, sgx = 0;  // the pair and staged kernels' grid.x
+  unsigned nblk_fill = 0;     // blocks per fill position (stats partials)
+};
+
+// eval_chunk's re-run requests to kueue_tas_eval_batch_ptrs (positive: never a KUEUE_TAS_E* code)
+enum ChunkRc : int {
+  ChunkGrowEntries = 1,  // an assignment exceeded the per-eval device capacity: grow entry_cap and re-run
+  ChunkRerun = 2,        // a class hash collision (exact merge) or a select list overflow (unbounded lists)
+};
+
+static void trace(kueue_tas_ctx* c, int k) { c->trace[k] = wall_ms(); }
+
+static size_t part_of(size_t n, size_t nparts, size_t i0) {  // the static part starting at request i0
+  size_t t = 0;
+  while (t + 1 < nparts && ktas_pool::HostPool::part_begin(n, t + 1, nparts) <= i0) t++;
+  return t;
+}
+
+// The staging arena's typed views
+static DevEval* stage_evals(kueue_tas_ctx* c, const ChunkPlan& p) { return reinterpret_cast<DevEval*>(c->h_stage.p + p.o.evals); }
+static DevTerm* stage_terms(kueue_tas_ctx* c, const ChunkPlan& p) { return reinterpret_cast<DevTerm*>(c->h_stage.p + p.o.terms); }
+static int32_t* stage_ints(kueue_tas_ctx* c, size_t off) { return reinterpret_cast<int32_t*>(c->h_stage.p + off); }
+static const int32_t* dev_ints(kueue_tas_ctx* c, size_t off) { return reinterpret_cast<const int32_t*>(c->d_stage.p + off); }
+
+// Phase-1 class keys: the hashes and exact compares of a request's signature
+// (terms, overlay, simulateEmpty, leader) and mask (slice parameters,
+// selectors, taint row, affinity) over the compiled records.
+struct ClassKeys {
+  const DevTerm* hterms;
+  const kueue_tas_assumed* assumed;
+  const kueue_tas_affinity_req* aff;
+  const int32_t* aff_vals;
+  const int32_t* taint_table;
+  size_t taint_table_len;
+  int32_t P;  // taint profiles
+  int L;      // levels
+  ClassKeys(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p)
+      : hterms(stage_terms(c, p)), assumed(a.assumed), aff(a.aff), aff_vals(a.aff_vals), taint_table(a.taint_table),
+        taint_table_len(a.taint_table_len), P(c->num_profiles), L(c->snap.L) {}
+
+  const int32_t* taint_row(const DevEval& e) const {
+    return (taint_table && size_t(e.taint_table) + size_t(P) <= taint_table_len) ? taint_table + e.taint_table
+                                                                                  : nullptr;
+  }
+  uint64_t sig_hash(const DevEval& e) const {
+    uint64_t h = 1469598103934665603ull;
+    auto add = [&](uint64_t v) {
+      h ^= v;
+      h *= 1099511628211ull;
+      h ^= h >> 31;
+    };
+    add(e.flags & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_SIMULATE_EMPTY));
+    add(uint64_t(uint32_t(e.nreq)) | (uint64_t(uint32_t(e.nlead)) << 32));
+    for (int k = 0; k < e.nreq + e.nlead; k++) {
+      const DevTerm& t = hterms[k < e.nreq ? e.term_begin + k : e.lead_begin + (k - e.nreq)];
+      add(uint64_t(uint32_t(t.col)));
+      add(uint64_t(t.val));
+    }
+    for (int a = e.assumed_begin; a < e.assumed_end; a++) {
+      add(uint64_t(uint32_t(assumed[a].leaf)) | (uint64_t(uint32_t(assumed[a].col)) << 32));
+      add(uint64_t(assumed[a].value));
+    }
+    return h;
+  }
+  uint64_t mask_hash(const DevEval& e) const {
+    uint64_t h = 0x9e3779b97f4a7c15ull;
+    auto add = [&](uint64_t v) {
+      h ^= v;
+      h *= 1099511628211ull;
+      h ^= h >> 29;
+    };
+    add(uint64_t(uint32_t(e.slice_size)) | (uint64_t(uint32_t(e.slice_level)) << 32));
+    for (int l = 0; l < L; l++) add(uint64_t(uint32_t(e.ssal[l])));  // no kernel reads a level >= L
+    add(uint64_t(uint32_t(e.nsel)));
+    add(uint64_t(uint32_t(e.dom_begin)) | (uint64_t(uint32_t(e.dom_end)) << 32));
+    for (int k = 0; k < e.nsel; k++) add(uint64_t(uint32_t(e.sel_col[k])) | (uint64_t(uint32_t(e.sel_val[k])) << 32));
+    if (const int32_t* row = taint_row(e))
+      for (int p = 0; p < P; p++) add(uint64_t(uint32_t(row[p])));
+    auto add_reqs = [&](int32_t rb, int32_t re) {
+      for (int k = rb; k < re; k++) {
+        const kueue_tas_affinity_req& q = aff[k];
+        add(uint64_t(uint32_t(q.term)) | (uint64_t(uint32_t(q.col)) << 32));
+        add(uint64_t(uint32_t(q.negate)) | (uint64_t(uint32_t(q.len)) << 32));
+        for (int j = 0; j < q.len; j++) add(uint64_t(uint32_t(aff_vals[q.begin + j])));
+      }
+    };
+    if (e.flags & KUEUE_TAS_F_AFFINITY) {
+      add(0xaff1u);
+      add_reqs(e.aff_begin, e.aff_end);
+    }
+    if (e.sx_begin >= 0) {
+      add(0x5e1eu);
+      add_reqs(e.sx_begin, e.sx_end);
+    }
+    return h;
+  }
+  // base signature: what the leaf's remaining capacity depends on (a fill chunk shares it)
+  bool same_base(const DevEval& x, const DevEval& y) const {
+    if ((x.flags ^ y.flags) & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_SIMULATE_EMPTY)) return false;
+    if (x.assumed_end - x.assumed_begin != y.assumed_end - y.assumed_begin) return false;
+    for (int a = 0; a < x.assumed_end - x.assumed_begin; a++) {
+      const kueue_tas_assumed& p = assumed[x.assumed_begin + a];
+      const kueue_tas_assumed& q = assumed[y.assumed_begin + a];
+      if (p.leaf != q.leaf || p.col != q.col || p.value != q.value) return false;
+    }
+    return true;
+  }
+  bool same_sig(const DevEval& x, const DevEval& y) const {
+    if (x.nreq != y.nreq || x.nlead != y.nlead) return false;
+    for (int k = 0; k < x.nreq + x.nlead; k++) {
+      const DevTerm& a = hterms[k < x.nreq ? x.term_begin + k : x.lead_begin + (k - x.nreq)];
+      const DevTerm& b2 = hterms[k < y.nreq ? y.term_begin + k : y.lead_begin + (k - y.nreq)];
+      if (a.col != b2.col || a.val != b2.val) return false;
+    }
+    return same_base(x, y);
+  }
+  bool same_mask(const DevEval& x, const DevEval& y) const {
+    if (x.slice_size != y.slice_size || x.slice_level != y.slice_level || x.nsel != y.nsel) return false;
+    if (x.dom_begin != y.dom_begin || x.dom_end != y.dom_end) return false;
+    for (int l = 0; l < L; l++)
+      if (x.ssal[l] != y.ssal[l]) return false;
+    for (int k = 0; k < x.nsel; k++)
+      if (x.sel_col[k] != y.sel_col[k] || x.sel_val[k] != y.sel_val[k]) return false;
+    const int32_t *rx = taint_row(x), *ry = taint_row(y);
+    if ((rx == nullptr) != (ry == nullptr)) return false;
+    if (!(rx == nullptr || rx == ry || memcmp(rx, ry, size_t(P) * 4) == 0)) return false;
+    auto same_reqs = [&](int32_t xb, int32_t xe, int32_t yb, int32_t ye) {
+      if (xe - xb != ye - yb) return false;
+      for (int k = 0; k < xe - xb; k++) {
+        const kueue_tas_affinity_req& p = aff[xb + k];
+        const kueue_tas_affinity_req& q = aff[yb + k];
+        if (p.term != q.term || p.col != q.col || p.negate != q.negate || p.len != q.len) return false;
+        if (p.begin != q.begin && memcmp(aff_vals + p.begin, aff_vals + q.begin, size_t(p.len) * 4) != 0) return false;
+      }
+      return true;
+    };
+    if ((x.sx_begin >= 0) != (y.sx_begin >= 0)) return false;
+    if (x.sx_begin >= 0 && !same_reqs(x.sx_begin, x.sx_end, y.sx_begin, y.sx_end)) return false;
+    const bool ax = (x.flags & KUEUE_TAS_F_AFFINITY) != 0, ay = (y.flags & KUEUE_TAS_F_AFFINITY) != 0;
+    if (ax != ay) return false;
+    if (!ax) return true;
+    return same_reqs(x.aff_begin, x.aff_end, y.aff_begin, y.aff_end);
+  }
+  bool fast_lfc(const DevEval& e, int32_t N) const {
+    return (e.flags & KUEUE_TAS_F_LFC) != 0 &&
+           (e.flags & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_REQUIRED | KUEUE_TAS_F_MULTILAYER)) == 0 &&
+           e.requested_level == L - 1 && e.slice_level == L - 1 && e.slice_size == 1 && e.count >= 0 && N > 0;
+  }
+};
+
+// Stage 1: validation and term counts over the worker pool (pass A); an error
+// is reported for the lowest request index.  Static parts: the same thread
+// handles the same requests in passes A and B (and the host layer's compile
+// and decode of the same workloads before and after), so their records stay
+// in that core's cache.
+static int validate_requests(kueue_tas_ctx* c, const ChunkArgs& a) {
   const DevSnap& s = c->snap;
-  double tm = wall_ms();
-  auto lap = [&](int k) {
-    const double t = wall_ms();
-    c->host_ms[k] += t - tm;
-    tm = t;
-  };
-  auto trace = [&](int k) { c->trace[k] = wall_ms(); };
-  trace(0);
-  // ---- per-request host work over the worker pool: validation and term
-  // counts (pass A), then the device records, division magic and the class
-  // hashes (pass B); errors are reported for the lowest request index ----
+  const kueue_tas_eval_req* const* reqs = a.reqs;
+  const size_t n = a.n, num_aff = a.num_aff, num_aff_vals = a.num_aff_vals, num_assumed = a.num_assumed;
+  const kueue_tas_assumed* assumed = a.assumed;
+  const kueue_tas_affinity_req* aff = a.aff;
+  const int32_t* aff_vals = a.aff_vals;
   ktas_pool::HostPool& pool = ktas_pool::HostPool::get();
-  // static parts: the same thread handles the same requests in both passes
-  // (and the host layer's compile and decode of the same workloads before
-  // and after), so their records stay in that core's cache
   const size_t nparts = pool.parts();
-  const size_t nchunk = nparts;
-  auto part_of = [&](size_t i0) -> size_t {  // the static part starting at request i0
-    size_t t = 0;
-    while (t + 1 < nparts && ktas_pool::HostPool::part_begin(n, t + 1, nparts) <= i0) t++;
-    return t;
-  };
-  std::vector<int64_t>& toff = c->req_term_off;  // first term slot of each request
+  std::vector<int64_t>& toff = c->req_term_off;  // each request's term count (layout_stage: its first term slot)
   toff.assign(n + 1, 0);
   std::vector<int32_t>& chunk_maxt = c->req_chunk_maxt;
-  chunk_maxt.assign(std::max<size_t>(nchunk, 1), 1);
-  std::vector<std::pair<size_t, std::string>>& errs = c->req_errs;  // per chunk: (first bad request, message)
-  errs.assign(std::max<size_t>(nchunk, 1), {SIZE_MAX, std::string()});
+  chunk_maxt.assign(std::max<size_t>(nparts, 1), 1);
+  std::vector<std::pair<size_t, std::string>>& errs = c->req_errs;  // per part: (first bad request, message)
+  errs.assign(std::max<size_t>(nparts, 1), {SIZE_MAX, std::string()});
   auto validate = [&](size_t i, std::string* msg) -> bool {
     const auto& r = *reqs[i];
     if (r.num_req < 0 || r.num_req > KUEUE_TAS_MAX_COLS || r.num_leader_req < 0 || r.num_leader_req > KUEUE_TAS_MAX_COLS)
@@ -2033,7 +2230,7 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     return true;
   };
   pool.run_static(n, [&](size_t i0, size_t i1) {
-    const size_t ch = part_of(i0);
+    const size_t ch = part_of(n, nparts, i0);
     std::string msg;
     int32_t mt = 1;  // this part's widest request, stored once (the parts' slots share a cache line)
     for (size_t i = i0; i < i1; i++) {
@@ -2046,163 +2243,44 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
   });
   for (auto& e : errs)
     if (e.first != SIZE_MAX) return fail(c, KUEUE_TAS_EINVAL, e.second);
-  c->host_ms[6] += wall_ms() - tm;
-  trace(1);
+  return KUEUE_TAS_OK;
+}
+
+// Stage 2: the term offsets, the staging arena's layout and allocation, and
+// the per-request class scratch pass B fills.
+static int layout_stage(kueue_tas_ctx* c, const ChunkArgs& a, ChunkPlan& p) {
+  const size_t n = a.n;
+  std::vector<int64_t>& toff = c->req_term_off;  // first term slot of each request
   for (size_t i = 0; i < n; i++) toff[i + 1] += toff[i];
-  const size_t nterms = size_t(toff[n]);
-  int maxt = 1;
-  for (int32_t m : chunk_maxt) maxt = std::max(maxt, m);
+  p.nterms = size_t(toff[n]);
+  p.maxt = 1;
+  for (int32_t m : c->req_chunk_maxt) p.maxt = std::max(p.maxt, m);
   size_t stage_bytes = 0;
   auto seg = [&](size_t bytes) {
     const size_t o = stage_bytes;
     stage_bytes += (bytes + 255) / 256 * 256;
     return o;
   };
-  const size_t o_evals = seg(n * sizeof(DevEval)), o_terms = seg(nterms * sizeof(DevTerm));
-  const size_t o_taint = seg(taint_table_len * 4), o_assumed = seg(num_assumed * sizeof(kueue_tas_assumed));
-  const size_t o_aff = seg(num_aff * sizeof(kueue_tas_affinity_req)), o_affv = seg(num_aff_vals * 4);
-  const size_t o_fill = seg(n * 4), o_fchunks = seg(n * 8), o_pairs = seg(n * 8), o_rep = seg(n * 4);
-  const size_t o_frun = seg(n * 4);
-  const size_t o_slot = seg(n * 4), o_lrep = seg(n * 4), o_fast = seg(n * 4), o_leafsel = seg(n * 4);
-  const size_t o_pidx = seg(n * 4), o_bf = seg(n * 4);
-  const size_t o_moff = seg((n + 1) * 4), o_mem = seg(n * 4);  // class members in fill order (CSR)
-  // rollup_top_kernel's level maxima (INT32_MIN) and per-class arrival counters (0)
-  const size_t o_top = seg(n * (kMaxLevels + 1) * 4);
-  const size_t o_sel = seg(n * sizeof(SelSlot));  // BestFit-side select slots' buffers
-  // last: the per-position fill records, uploaded up to the batch's nfill
-  const size_t o_fpos = seg(n * sizeof(FillPos));
+  ArenaOffsets& o = p.o;  // (in this order: the upload is one copy of [0, fpos + nfill records))
+  o.evals = seg(n * sizeof(DevEval)), o.terms = seg(p.nterms * sizeof(DevTerm));
+  o.taint = seg(a.taint_table_len * 4), o.assumed = seg(a.num_assumed * sizeof(kueue_tas_assumed));
+  o.aff = seg(a.num_aff * sizeof(kueue_tas_affinity_req)), o.affv = seg(a.num_aff_vals * 4);
+  o.fill = seg(n * 4), o.fchunks = seg(n * 8), o.pairs = seg(n * 8), o.rep = seg(n * 4);
+  o.frun = seg(n * 4);
+  o.slot = seg(n * 4), o.lrep = seg(n * 4), o.fast = seg(n * 4), o.leafsel = seg(n * 4);
+  o.pidx = seg(n * 4), o.bf = seg(n * 4);
+  o.moff = seg((n + 1) * 4), o.mem = seg(n * 4);
+  o.top = seg(n * (kMaxLevels + 1) * 4);
+  o.sel = seg(n * sizeof(SelSlot));
+  o.fpos = seg(n * sizeof(FillPos));
   HIPCHK(c, c->h_stage.ensure(stage_bytes));
   HIPCHK(c, c->d_stage.ensure(stage_bytes));
-  uint8_t* hs = c->h_stage.p;
-  DevEval* hev = reinterpret_cast<DevEval*>(hs + o_evals);
-  DevTerm* hterms = reinterpret_cast<DevTerm*>(hs + o_terms);
-  // ---- class hashes (phase-1 classes below) ----
-  const int32_t P = c->num_profiles;
-  auto taint_row = [&](const DevEval& e) -> const int32_t* {
-    return (taint_table && size_t(e.taint_table) + size_t(P) <= taint_table_len) ? taint_table + e.taint_table
-                                                                                  : nullptr;
-  };
-  auto sig_hash = [&](const DevEval& e) {
-    uint64_t h = 1469598103934665603ull;
-    auto add = [&](uint64_t v) {
-      h ^= v;
-      h *= 1099511628211ull;
-      h ^= h >> 31;
-    };
-    add(e.flags & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_SIMULATE_EMPTY));
-    add(uint64_t(uint32_t(e.nreq)) | (uint64_t(uint32_t(e.nlead)) << 32));
-    for (int k = 0; k < e.nreq + e.nlead; k++) {
-      const DevTerm& t = hterms[k < e.nreq ? e.term_begin + k : e.lead_begin + (k - e.nreq)];
-      add(uint64_t(uint32_t(t.col)));
-      add(uint64_t(t.val));
-    }
-    for (int a = e.assumed_begin; a < e.assumed_end; a++) {
-      add(uint64_t(uint32_t(assumed[a].leaf)) | (uint64_t(uint32_t(assumed[a].col)) << 32));
-      add(uint64_t(assumed[a].value));
-    }
-    return h;
-  };
-  auto mask_hash = [&](const DevEval& e) {
-    uint64_t h = 0x9e3779b97f4a7c15ull;
-    auto add = [&](uint64_t v) {
-      h ^= v;
-      h *= 1099511628211ull;
-      h ^= h >> 29;
-    };
-    add(uint64_t(uint32_t(e.slice_size)) | (uint64_t(uint32_t(e.slice_level)) << 32));
-    for (int l = 0; l < s.L; l++) add(uint64_t(uint32_t(e.ssal[l])));  // no kernel reads a level >= L
-    add(uint64_t(uint32_t(e.nsel)));
-    add(uint64_t(uint32_t(e.dom_begin)) | (uint64_t(uint32_t(e.dom_end)) << 32));
-    for (int k = 0; k < e.nsel; k++) add(uint64_t(uint32_t(e.sel_col[k])) | (uint64_t(uint32_t(e.sel_val[k])) << 32));
-    if (const int32_t* row = taint_row(e))
-      for (int p = 0; p < P; p++) add(uint64_t(uint32_t(row[p])));
-    auto add_reqs = [&](int32_t rb, int32_t re) {
-      for (int k = rb; k < re; k++) {
-        const kueue_tas_affinity_req& q = aff[k];
-        add(uint64_t(uint32_t(q.term)) | (uint64_t(uint32_t(q.col)) << 32));
-        add(uint64_t(uint32_t(q.negate)) | (uint64_t(uint32_t(q.len)) << 32));
-        for (int j = 0; j < q.len; j++) add(uint64_t(uint32_t(aff_vals[q.begin + j])));
-      }
-    };
-    if (e.flags & KUEUE_TAS_F_AFFINITY) {
-      add(0xaff1u);
-      add_reqs(e.aff_begin, e.aff_end);
-    }
-    if (e.sx_begin >= 0) {
-      add(0x5e1eu);
-      add_reqs(e.sx_begin, e.sx_end);
-    }
-    return h;
-  };
-  auto same_sig = [&](const DevEval& x, const DevEval& y) {
-    if ((x.flags ^ y.flags) & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_SIMULATE_EMPTY)) return false;
-    if (x.nreq != y.nreq || x.nlead != y.nlead) return false;
-    for (int k = 0; k < x.nreq + x.nlead; k++) {
-      const DevTerm& a = hterms[k < x.nreq ? x.term_begin + k : x.lead_begin + (k - x.nreq)];
-      const DevTerm& b2 = hterms[k < y.nreq ? y.term_begin + k : y.lead_begin + (k - y.nreq)];
-      if (a.col != b2.col || a.val != b2.val) return false;
-    }
-    if (x.assumed_end - x.assumed_begin != y.assumed_end - y.assumed_begin) return false;
-    for (int a = 0; a < x.assumed_end - x.assumed_begin; a++) {
-      const kueue_tas_assumed& p = assumed[x.assumed_begin + a];
-      const kueue_tas_assumed& q = assumed[y.assumed_begin + a];
-      if (p.leaf != q.leaf || p.col != q.col || p.value != q.value) return false;
-    }
-    return true;
-  };
-  // base signature: what the leaf's remaining capacity depends on (a fill chunk shares it)
-  auto same_base = [&](const DevEval& x, const DevEval& y) {
-    if ((x.flags ^ y.flags) & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_SIMULATE_EMPTY)) return false;
-    if (x.assumed_end - x.assumed_begin != y.assumed_end - y.assumed_begin) return false;
-    for (int a = 0; a < x.assumed_end - x.assumed_begin; a++) {
-      const kueue_tas_assumed& p = assumed[x.assumed_begin + a];
-      const kueue_tas_assumed& q = assumed[y.assumed_begin + a];
-      if (p.leaf != q.leaf || p.col != q.col || p.value != q.value) return false;
-    }
-    return true;
-  };
-  auto same_mask = [&](const DevEval& x, const DevEval& y) {
-    if (x.slice_size != y.slice_size || x.slice_level != y.slice_level || x.nsel != y.nsel) return false;
-    if (x.dom_begin != y.dom_begin || x.dom_end != y.dom_end) return false;
-    for (int l = 0; l < s.L; l++)
-      if (x.ssal[l] != y.ssal[l]) return false;
-    for (int k = 0; k < x.nsel; k++)
-      if (x.sel_col[k] != y.sel_col[k] || x.sel_val[k] != y.sel_val[k]) return false;
-    const int32_t *rx = taint_row(x), *ry = taint_row(y);
-    if ((rx == nullptr) != (ry == nullptr)) return false;
-    if (!(rx == nullptr || rx == ry || memcmp(rx, ry, size_t(P) * 4) == 0)) return false;
-    auto same_reqs = [&](int32_t xb, int32_t xe, int32_t yb, int32_t ye) {
-      if (xe - xb != ye - yb) return false;
-      for (int k = 0; k < xe - xb; k++) {
-        const kueue_tas_affinity_req& p = aff[xb + k];
-        const kueue_tas_affinity_req& q = aff[yb + k];
-        if (p.term != q.term || p.col != q.col || p.negate != q.negate || p.len != q.len) return false;
-        if (p.begin != q.begin && memcmp(aff_vals + p.begin, aff_vals + q.begin, size_t(p.len) * 4) != 0) return false;
-      }
-      return true;
-    };
-    if ((x.sx_begin >= 0) != (y.sx_begin >= 0)) return false;
-    if (x.sx_begin >= 0 && !same_reqs(x.sx_begin, x.sx_end, y.sx_begin, y.sx_end)) return false;
-    const bool ax = (x.flags & KUEUE_TAS_F_AFFINITY) != 0, ay = (y.flags & KUEUE_TAS_F_AFFINITY) != 0;
-    if (ax != ay) return false;
-    if (!ax) return true;
-    return same_reqs(x.aff_begin, x.aff_end, y.aff_begin, y.aff_end);
-  };
-  auto fast_lfc = [&](const DevEval& e) {
-    return (e.flags & KUEUE_TAS_F_LFC) != 0 &&
-           (e.flags & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_REQUIRED | KUEUE_TAS_F_MULTILAYER)) == 0 &&
-           e.requested_level == s.L - 1 && e.slice_level == s.L - 1 && e.slice_size == 1 && e.count >= 0 && s.N > 0;
-  };
-  std::vector<uint64_t>& h_sig = c->req_sig_hash;   // signature hash per request
-  std::vector<uint64_t>& h_cls = c->req_cls_hash;   // signature x mask hash per request
-  h_sig.resize(n);
-  h_cls.resize(n);
-  std::vector<uint8_t>& req_fast = c->req_fast;     // fast-LFC eligible (fast_lfc)
-  std::vector<uint8_t>& req_leaf = c->req_leaf;     // requested level == the leaf level
-  std::vector<int32_t>& req_local_cls = c->req_local_cls;  // class within the request's static part
-  req_fast.resize(n);
-  req_leaf.resize(n);
-  req_local_cls.resize(n);
+  const size_t nparts = ktas_pool::HostPool::get().parts();
+  c->req_sig_hash.resize(n);   // signature hash per request
+  c->req_cls_hash.resize(n);   // signature x mask hash per request
+  c->req_fast.resize(n);       // fast-LFC eligible (ClassKeys::fast_lfc)
+  c->req_leaf.resize(n);       // requested level == the leaf level
+  c->req_local_cls.resize(n);  // class within the request's static part
   c->part_cls.resize(nparts);
   for (size_t t = 0; t < nparts; t++) {
     PartClasses& pc = c->part_cls[t];
@@ -2212,12 +2290,30 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     pc.hcls.clear();
     pc.hsig.clear();
   }
-  trace(2);
-  // ---- compile requests to device form (magic numbers) ----
-  const double t_b = wall_ms();
+  return KUEUE_TAS_OK;
+}
+
+// Stage 3: requests to device form over the worker pool (pass B): records,
+// division magic, class hashes and each static part's classes.
+static int compile_requests(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p) {
+  const DevSnap& s = c->snap;
+  const kueue_tas_eval_req* const* reqs = a.reqs;
+  const size_t n = a.n;
+  ktas_pool::HostPool& pool = ktas_pool::HostPool::get();
+  const size_t nparts = pool.parts();
+  DevEval* hev = stage_evals(c, p);
+  DevTerm* hterms = stage_terms(c, p);
+  const ClassKeys keys(c, a, p);
+  const std::vector<int64_t>& toff = c->req_term_off;
+  std::vector<std::pair<size_t, std::string>>& errs = c->req_errs;
+  std::vector<uint64_t>& h_sig = c->req_sig_hash;
+  std::vector<uint64_t>& h_cls = c->req_cls_hash;
+  std::vector<uint8_t>& req_fast = c->req_fast;
+  std::vector<uint8_t>& req_leaf = c->req_leaf;
+  std::vector<int32_t>& req_local_cls = c->req_local_cls;
   if (c->magic_cache.size() < nparts) c->magic_cache.resize(nparts);
   pool.run_static(n, [&](size_t i0, size_t i1) {
-    const size_t ch = part_of(i0);
+    const size_t ch = part_of(n, nparts, i0);
     MagicCache& mc = c->magic_cache[ch];
     for (size_t i = i0; i < i1; i++) {
       const auto& r = *reqs[i];
@@ -2282,9 +2378,9 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
         if (errs[ch].first == SIZE_MAX) errs[ch] = {i, "leader columns"};
         continue;
       }
-      h_sig[i] = sig_hash(e);
-      h_cls[i] = h_sig[i] ^ (mask_hash(e) * 0xff51afd7ed558ccdull);
-      req_fast[i] = fast_lfc(e) ? 1 : 0;
+      h_sig[i] = keys.sig_hash(e);
+      h_cls[i] = h_sig[i] ^ (keys.mask_hash(e) * 0xff51afd7ed558ccdull);
+      req_fast[i] = keys.fast_lfc(e, s.N) ? 1 : 0;
       req_leaf[i] = e.requested_level == s.L - 1 ? 1 : 0;
       // this part's classes (first member in request order), exact compare on a hash hit
       PartClasses& pc = c->part_cls[ch];
@@ -2292,7 +2388,7 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
       int32_t* head = pc.head.find(h_cls[i]);
       for (int32_t q = *head; q >= 0; q = pc.next[size_t(q)]) {
         const DevEval& r = hev[pc.rep[size_t(q)]];
-        if (same_sig(e, r) && same_mask(e, r)) {
+        if (keys.same_sig(e, r) && keys.same_mask(e, r)) {
           k = q;
           break;
         }
@@ -2310,96 +2406,94 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
   });
   for (auto& e : errs)
     if (e.first != SIZE_MAX) return fail(c, KUEUE_TAS_EINVAL, e.second);
-  c->host_ms[7] += wall_ms() - t_b;
-  trace(3);
-  if (taint_table_len) memcpy(hs + o_taint, taint_table, taint_table_len * 4);
-  if (num_assumed) memcpy(hs + o_assumed, assumed, num_assumed * sizeof(kueue_tas_assumed));
-  if (num_aff) memcpy(hs + o_aff, aff, num_aff * sizeof(kueue_tas_affinity_req));
-  if (num_aff_vals) memcpy(hs + o_affv, aff_vals, num_aff_vals * 4);
-  lap(0);
-  trace(4);
+  return KUEUE_TAS_OK;
+}
 
-  // Phase-1 classes: evals with identical phase-1 inputs (request terms,
-  // masks, overlay, slice parameters) get identical counters; phase 1 runs
-  // once per class (its representative).  Every member's select reads the
-  // class counters and keeps its mutations in a private overlay; duplicates
-  // only get the rep's exclusion stats.  A class's request signature (terms,
-  // overlay, simulateEmpty, leader) decides which classes share a fill chunk.
-  int32_t* h_fill = reinterpret_cast<int32_t*>(hs + o_fill);
-  int32_t* h_fchunks = reinterpret_cast<int32_t*>(hs + o_fchunks);
-  int32_t* h_pairs = reinterpret_cast<int32_t*>(hs + o_pairs);
-  int32_t* h_rep = reinterpret_cast<int32_t*>(hs + o_rep);
-  int32_t* h_slot = reinterpret_cast<int32_t*>(hs + o_slot);
-  int32_t* h_lrep = reinterpret_cast<int32_t*>(hs + o_lrep);
-  int32_t* h_fast = reinterpret_cast<int32_t*>(hs + o_fast);
-  int32_t* h_leafsel = reinterpret_cast<int32_t*>(hs + o_leafsel);
-  int32_t* h_pidx = reinterpret_cast<int32_t*>(hs + o_pidx);  // eval -> row of its leaf partials, -1
-  int32_t* h_bf = reinterpret_cast<int32_t*>(hs + o_bf);      // evals selected on the main stream
-  int nbf = 0;
-  int nfill = 0, npairs = 0, nslots = 0, nfast = 0, nfchunks = 0, nleafsel = 0, nruns = 0, nsingle = 0;
-  {
-    // classes: open hash chains on the 64-bit (signature, mask) hash, exact compare on the rep
-    std::vector<int32_t>& cls_rep = c->cls_rep;    // first member of each class
-    std::vector<int32_t>& cls_sig = c->cls_sig;    // signature id of each class
-    std::vector<int32_t>& cls_of = c->cls_of;      // class of each eval
-    std::vector<int32_t>& sig_rep = c->sig_rep;    // first eval of each signature
-    cls_rep.clear();
-    cls_sig.clear();
-    sig_rep.clear();
-    cls_of.assign(n, -1);
-    FlatMap& cls_head = c->cls_head;
-    FlatMap& sig_head = c->sig_head;
-    cls_head.reset(n);
-    sig_head.reset(n);
-    std::vector<int32_t>& cls_next = c->cls_next;  // chain of classes with the same hash
-    std::vector<int32_t>& sig_next = c->sig_next;
-    cls_next.clear();
-    sig_next.clear();
-    // the parts' classes merged in part order: a global class is numbered by
-    // its first member, as a serial pass over the requests would number it
-    std::vector<int32_t>& part_map = c->part_map;  // (part, local class) -> global class
-    std::vector<size_t>& part_base = c->part_base;
-    part_base.assign(nparts + 1, 0);
-    for (size_t t = 0; t < nparts; t++) part_base[t + 1] = part_base[t] + c->part_cls[t].rep.size();
-    part_map.assign(part_base[nparts], -1);
-    // Speculative merge: parts' classes with equal 64-bit hashes are taken
-    // as equal here, and verified exactly while the device runs (the exact
-    // compares read other cores' records: ~0.2 us each on the critical path);
-    // a hash collision re-runs the chunk with this exact merge (exact_merge)
-    if (!c->exact_merge) {
-      for (size_t t = 0; t < nparts; t++) {
-        const PartClasses& pc = c->part_cls[t];
-        for (size_t j = 0; j < pc.rep.size(); j++) {
-          int32_t* head = cls_head.find(c->collide_test ? 0 : pc.hcls[j]);
-          int32_t k = *head;
-          if (k < 0) {
-            k = int32_t(cls_rep.size());
-            cls_rep.push_back(pc.rep[j]);
-            cls_next.push_back(-1);
-            *head = k;
-            int32_t* shead = sig_head.find(c->collide_test ? 0 : pc.hsig[j]);
-            if (*shead < 0) {
-              *shead = int32_t(sig_rep.size());
-              sig_rep.push_back(pc.rep[j]);
-              sig_next.push_back(-1);
-            }
-            cls_sig.push_back(*shead);
+// the caller's tables into the staging arena
+static void copy_tables(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p) {
+  uint8_t* hs = c->h_stage.p;
+  if (a.taint_table_len) memcpy(hs + p.o.taint, a.taint_table, a.taint_table_len * 4);
+  if (a.num_assumed) memcpy(hs + p.o.assumed, a.assumed, a.num_assumed * sizeof(kueue_tas_assumed));
+  if (a.num_aff) memcpy(hs + p.o.aff, a.aff, a.num_aff * sizeof(kueue_tas_affinity_req));
+  if (a.num_aff_vals) memcpy(hs + p.o.affv, a.aff_vals, a.num_aff_vals * 4);
+}
+
+// Phase-1 classes (stages 4 to 6): evals with identical phase-1 inputs
+// (request terms, masks, overlay, slice parameters) get identical counters;
+// phase 1 runs once per class (its representative).  Every member's select
+// reads the class counters and keeps its mutations in a private overlay;
+// duplicates only get the rep's exclusion stats.  A class's request signature
+// (terms, overlay, simulateEmpty, leader) decides which classes share a fill
+// chunk.
+
+// Stage 4: the parts' classes merged into the chunk's classes and signatures
+// (cls_rep, cls_sig, sig_rep) and each eval's class (cls_of): open hash chains
+// on the 64-bit (signature, mask) hash, exact compare on the rep.
+static void merge_classes(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p) {
+  const size_t n = a.n;
+  const size_t nparts = ktas_pool::HostPool::get().parts();
+  const DevEval* hev = stage_evals(c, p);
+  const ClassKeys keys(c, a, p);
+  std::vector<int32_t>& cls_rep = c->cls_rep;    // first member of each class
+  std::vector<int32_t>& cls_sig = c->cls_sig;    // signature id of each class
+  std::vector<int32_t>& cls_of = c->cls_of;      // class of each eval
+  std::vector<int32_t>& sig_rep = c->sig_rep;    // first eval of each signature
+  cls_rep.clear();
+  cls_sig.clear();
+  sig_rep.clear();
+  cls_of.assign(n, -1);
+  FlatMap& cls_head = c->cls_head;
+  FlatMap& sig_head = c->sig_head;
+  cls_head.reset(n);
+  sig_head.reset(n);
+  std::vector<int32_t>& cls_next = c->cls_next;  // chain of classes with the same hash
+  std::vector<int32_t>& sig_next = c->sig_next;
+  cls_next.clear();
+  sig_next.clear();
+  // the parts' classes merged in part order: a global class is numbered by
+  // its first member, as a serial pass over the requests would number it
+  std::vector<int32_t>& part_map = c->part_map;  // (part, local class) -> global class
+  std::vector<size_t>& part_base = c->part_base;
+  part_base.assign(nparts + 1, 0);
+  for (size_t t = 0; t < nparts; t++) part_base[t + 1] = part_base[t] + c->part_cls[t].rep.size();
+  part_map.assign(part_base[nparts], -1);
+  // Speculative merge: parts' classes with equal 64-bit hashes are taken
+  // as equal here, and verified exactly while the device runs (verify_merge;
+  // the exact compares read other cores' records: ~0.2 us each on the
+  // critical path); a hash collision re-runs the chunk with the exact merge
+  // below (exact_merge)
+  if (!c->exact_merge) {
+    for (size_t t = 0; t < nparts; t++) {
+      const PartClasses& pc = c->part_cls[t];
+      for (size_t j = 0; j < pc.rep.size(); j++) {
+        int32_t* head = cls_head.find(c->collide_test ? 0 : pc.hcls[j]);
+        int32_t k = *head;
+        if (k < 0) {
+          k = int32_t(cls_rep.size());
+          cls_rep.push_back(pc.rep[j]);
+          cls_next.push_back(-1);
+          *head = k;
+          int32_t* shead = sig_head.find(c->collide_test ? 0 : pc.hsig[j]);
+          if (*shead < 0) {
+            *shead = int32_t(sig_rep.size());
+            sig_rep.push_back(pc.rep[j]);
+            sig_next.push_back(-1);
           }
-          part_map[part_base[t] + j] = k;
+          cls_sig.push_back(*shead);
         }
+        part_map[part_base[t] + j] = k;
       }
     }
-    for (size_t t = 0; t < nparts && c->exact_merge; t++)
+  }
+  for (size_t t = 0; t < nparts && c->exact_merge; t++)
     for (size_t j = 0; j < c->part_cls[t].rep.size(); j++) {
       const size_t i = size_t(c->part_cls[t].rep[j]);
       const DevEval& e = hev[i];
-      const uint64_t hs1 = h_sig[i];
-      const uint64_t hc = h_cls[i];
       int32_t k = -1;
-      int32_t* head = cls_head.find(hc);
+      int32_t* head = cls_head.find(c->req_cls_hash[i]);
       for (int32_t q = *head; q >= 0; q = cls_next[size_t(q)]) {
         const DevEval& r = hev[cls_rep[size_t(q)]];
-        if (same_sig(e, r) && same_mask(e, r)) {
+        if (keys.same_sig(e, r) && keys.same_mask(e, r)) {
           k = q;
           break;
         }
@@ -2410,9 +2504,9 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
         cls_next.push_back(*head);
         *head = k;
         int32_t sg = -1;
-        int32_t* shead = sig_head.find(hs1);
+        int32_t* shead = sig_head.find(c->req_sig_hash[i]);
         for (int32_t q = *shead; q >= 0; q = sig_next[size_t(q)])
-          if (same_sig(e, hev[sig_rep[size_t(q)]])) {
+          if (keys.same_sig(e, hev[sig_rep[size_t(q)]])) {
             sg = q;
             break;
           }
@@ -2426,160 +2520,211 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
       }
       part_map[part_base[t] + j] = k;
     }
-    for (size_t t = 0; t < nparts; t++)
-      for (size_t i = ktas_pool::HostPool::part_begin(n, t, nparts); i < ktas_pool::HostPool::part_begin(n, t + 1, nparts); i++)
-        cls_of[i] = part_map[part_base[t] + size_t(req_local_cls[i])];
-    trace(5);
-    const int ncls = int(cls_rep.size());
-    // representative: the first fast-LFC member if any (its class gets an LFC table slot)
-    std::vector<int32_t>& rep = c->cls_fastrep;
-    rep.assign(size_t(ncls), -1);
-    for (size_t i = 0; i < n; i++) {
-      const int32_t k = cls_of[i];
-      if (rep[size_t(k)] < 0 && req_fast[i]) rep[size_t(k)] = int32_t(i);
-    }
-    std::vector<int32_t>& slot_of = c->cls_slot;
-    slot_of.assign(size_t(ncls), -1);
-    for (int k = 0; k < ncls; k++) {
-      if (rep[size_t(k)] >= 0) {
-        slot_of[size_t(k)] = nslots;
-        h_lrep[nslots++] = rep[size_t(k)];
-      } else {
-        rep[size_t(k)] = cls_rep[size_t(k)];
-      }
-    }
-    for (size_t i = 0; i < n; i++) {
-      const int32_t k = cls_of[i], r = rep[size_t(k)];
-      const bool fast = slot_of[size_t(k)] >= 0 && req_fast[i];
-      h_rep[i] = r;
-      h_slot[i] = fast ? slot_of[size_t(k)] : -1;
-      if (fast) h_fast[nfast++] = int32_t(i);
-      else h_bf[nbf++] = int32_t(i);
-      if (int32_t(i) != r) {
-        h_pairs[2 * npairs] = r;
-        h_pairs[2 * npairs + 1] = ~int32_t(i);  // exclusion stats only
-        npairs++;
-      }
-      h_pidx[i] = -1;
-      if (req_leaf[i] && !fast) {
-        h_pidx[i] = nleafsel;
-        h_leafsel[nleafsel++] = int32_t(i);
-      }
-    }
-    trace(6);
-    // fill chunks: classes ordered by (base signature, signature), <= kEvalsPerFillBlock
-    // per chunk, one base signature each (the leaf's remaining capacity is
-    // shared); a run of one signature inside a chunk shares the CountIn
-    const int nsig = int(sig_rep.size());
-    std::vector<int32_t>& sig_base = c->sig_base;
-    sig_base.assign(size_t(nsig), -1);
-    {
-      std::vector<int32_t>& base_rep = c->base_rep;
-      base_rep.clear();
-      for (int g = 0; g < nsig; g++) {
-        const DevEval& e = hev[sig_rep[size_t(g)]];
-        for (size_t q = 0; q < base_rep.size() && sig_base[size_t(g)] < 0; q++)
-          if (same_base(e, hev[base_rep[q]])) sig_base[size_t(g)] = int32_t(q);
-        if (sig_base[size_t(g)] < 0) {
-          sig_base[size_t(g)] = int32_t(base_rep.size());
-          base_rep.push_back(sig_rep[size_t(g)]);
-        }
-        if (base_rep.size() > 64) {  // many distinct bases (assumed usage per eval): no sharing to look for
-          for (int h = g + 1; h < nsig; h++) sig_base[size_t(h)] = int32_t(base_rep.size()) + (h - g - 1);
-          break;
-        }
-      }
-    }
-    std::vector<int32_t>& order = c->cls_order;
-    order.resize(size_t(ncls));
-    for (int k = 0; k < ncls; k++) order[size_t(k)] = k;
-    std::vector<int32_t>& sig_ncls = c->sig_ncls;  // classes per signature: small ones pack together
-    sig_ncls.assign(size_t(nsig), 0);
-    for (int k = 0; k < ncls; k++) sig_ncls[size_t(cls_sig[size_t(k)])]++;
-    auto small = [&](int32_t sg) { return sig_ncls[size_t(sg)] < kEvalsPerFillBlock / 2; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b2) {
-      const int32_t sa = cls_sig[size_t(a)], sb = cls_sig[size_t(b2)];
-      const int32_t ba = sig_base[size_t(sa)], bb = sig_base[size_t(sb)];
-      if (ba != bb) return ba < bb;
-      if (small(sa) != small(sb)) return !small(sa);
-      return sa < sb;
-    });
-    trace(7);
-    for (int k = 0; k < ncls; k++) h_fill[k] = rep[size_t(order[size_t(k)])];
-    nfill = ncls;
-    {  // members other than the rep, grouped by fill position (stats written by the reduce)
-      int32_t* h_moff = reinterpret_cast<int32_t*>(hs + o_moff);
-      int32_t* h_mem = reinterpret_cast<int32_t*>(hs + o_mem);
-      std::vector<int32_t>& pos = c->cls_pos;
-      pos.resize(size_t(ncls));
-      for (int k = 0; k < ncls; k++) pos[size_t(order[size_t(k)])] = k;
-      for (int k = 0; k <= ncls; k++) h_moff[k] = 0;
-      for (size_t i = 0; i < n; i++)
-        if (int32_t(i) != rep[size_t(cls_of[i])]) h_moff[pos[size_t(cls_of[i])] + 1]++;
-      for (int k = 0; k < ncls; k++) h_moff[k + 1] += h_moff[k];
-      std::vector<int32_t>& cur = c->cls_cur;
-      cur.assign(h_moff, h_moff + ncls);
-      for (size_t i = 0; i < n; i++)
-        if (int32_t(i) != rep[size_t(cls_of[i])]) h_mem[cur[size_t(pos[size_t(cls_of[i])])]++] = int32_t(i);
-    }
-    {  // counters are stored per class, row = fill position: evals and LFC tables refer to their class's row
-      const std::vector<int32_t>& pos = c->cls_pos;
-      for (size_t i = 0; i < n; i++) h_rep[i] = pos[size_t(cls_of[i])];
-      for (int k = 0; k < ncls; k++)
-        if (slot_of[size_t(k)] >= 0) h_lrep[slot_of[size_t(k)]] = pos[size_t(k)];
-    }
-    trace(8);
-    int32_t* h_frun = reinterpret_cast<int32_t*>(hs + o_frun);
-    // a signature with at least half a chunk of classes gets chunks of its
-    // own (one run: CountIn before the eval loop); the smaller ones of a base
-    // share packed chunks (several runs).  Single-run chunks first.
-    std::vector<int32_t>& packed = c->cls_packed;  // [start, len) signature runs left for packing
-    packed.clear();
-    for (int k = 0; k < ncls;) {
-      const int32_t sg = cls_sig[size_t(order[size_t(k)])];
-      int e = k + 1;
-      while (e < ncls && cls_sig[size_t(order[size_t(e)])] == sg) e++;
-      if (e - k >= kEvalsPerFillBlock / 2) {
-        for (int q = k; q < e; q += kEvalsPerFillBlock) {
-          h_fchunks[2 * nfchunks] = q;
-          h_fchunks[2 * nfchunks + 1] = std::min(kEvalsPerFillBlock, e - q);
-          nfchunks++;
-          for (int r = q; r < q + h_fchunks[2 * nfchunks - 1]; r++) h_frun[r] = nruns;
-          nruns++;
-        }
-      } else {
-        packed.push_back(k);
-        packed.push_back(e - k);
-      }
-      k = e;
-    }
-    nsingle = nfchunks;
-    for (size_t i = 0; i < packed.size();) {  // runs of one base, in order, up to a chunk each
-      const int32_t k0 = packed[i];
-      const int32_t base = sig_base[size_t(cls_sig[size_t(order[size_t(k0)])])];
-      int len = 0;
-      h_fchunks[2 * nfchunks] = k0;
-      while (i < packed.size() && len + packed[i + 1] <= kEvalsPerFillBlock && packed[i] == k0 + len &&
-             sig_base[size_t(cls_sig[size_t(order[size_t(packed[i])])])] == base) {
-        for (int r = packed[i]; r < packed[i] + packed[i + 1]; r++) h_frun[r] = nruns;
-        nruns++;
-        len += packed[i + 1];
-        i += 2;
-      }
-      h_fchunks[2 * nfchunks + 1] = len;
-      nfchunks++;
+  for (size_t t = 0; t < nparts; t++)
+    for (size_t i = ktas_pool::HostPool::part_begin(n, t, nparts); i < ktas_pool::HostPool::part_begin(n, t + 1, nparts); i++)
+      cls_of[i] = part_map[part_base[t] + size_t(c->req_local_cls[i])];
+}
+
+// Stage 5: each class's representative (the first fast-LFC member if any: its
+// class gets an LFC table slot) and the per-eval index lists of the arena.
+static void assign_reps_and_slots(kueue_tas_ctx* c, const ChunkArgs& a, ChunkPlan& p) {
+  const size_t n = a.n;
+  const std::vector<int32_t>& cls_of = c->cls_of;
+  const std::vector<uint8_t>& req_fast = c->req_fast;
+  const std::vector<uint8_t>& req_leaf = c->req_leaf;
+  int32_t* h_pairs = stage_ints(c, p.o.pairs);
+  int32_t* h_rep = stage_ints(c, p.o.rep);
+  int32_t* h_slot = stage_ints(c, p.o.slot);
+  int32_t* h_lrep = stage_ints(c, p.o.lrep);
+  int32_t* h_fast = stage_ints(c, p.o.fast);
+  int32_t* h_leafsel = stage_ints(c, p.o.leafsel);
+  int32_t* h_pidx = stage_ints(c, p.o.pidx);  // eval -> row of its leaf partials, -1
+  int32_t* h_bf = stage_ints(c, p.o.bf);      // evals selected on the main stream
+  int nslots = 0, nfast = 0, nbf = 0, npairs = 0, nleafsel = 0;
+  const int ncls = int(c->cls_rep.size());
+  std::vector<int32_t>& rep = c->cls_fastrep;
+  rep.assign(size_t(ncls), -1);
+  for (size_t i = 0; i < n; i++) {
+    const int32_t k = cls_of[i];
+    if (rep[size_t(k)] < 0 && req_fast[i]) rep[size_t(k)] = int32_t(i);
+  }
+  std::vector<int32_t>& slot_of = c->cls_slot;
+  slot_of.assign(size_t(ncls), -1);
+  for (int k = 0; k < ncls; k++) {
+    if (rep[size_t(k)] >= 0) {
+      slot_of[size_t(k)] = nslots;
+      h_lrep[nslots++] = rep[size_t(k)];
+    } else {
+      rep[size_t(k)] = c->cls_rep[size_t(k)];
     }
   }
-  lap(1);
-  trace(9);
+  for (size_t i = 0; i < n; i++) {
+    const int32_t k = cls_of[i], r = rep[size_t(k)];
+    const bool fast = slot_of[size_t(k)] >= 0 && req_fast[i];
+    h_rep[i] = r;
+    h_slot[i] = fast ? slot_of[size_t(k)] : -1;
+    if (fast) h_fast[nfast++] = int32_t(i);
+    else h_bf[nbf++] = int32_t(i);
+    if (int32_t(i) != r) {
+      h_pairs[2 * npairs] = r;
+      h_pairs[2 * npairs + 1] = ~int32_t(i);  // exclusion stats only
+      npairs++;
+    }
+    h_pidx[i] = -1;
+    if (req_leaf[i] && !fast) {
+      h_pidx[i] = nleafsel;
+      h_leafsel[nleafsel++] = int32_t(i);
+    }
+  }
+  p.nslots = nslots;
+  p.nfast = nfast;
+  p.nbf = nbf;
+  p.npairs = npairs;
+  p.nleafsel = nleafsel;
+}
+
+// Stage 6: fill chunks: classes ordered by (base signature, signature),
+// <= kEvalsPerFillBlock per chunk, one base signature each (the leaf's
+// remaining capacity is shared); a run of one signature inside a chunk shares
+// the CountIn.  Trace points 7 (order) and 8 (member lists) lie inside.
+static void order_fill_chunks(kueue_tas_ctx* c, const ChunkArgs& a, ChunkPlan& p) {
+  const size_t n = a.n;
+  const DevEval* hev = stage_evals(c, p);
+  const ClassKeys keys(c, a, p);
+  const std::vector<int32_t>& cls_sig = c->cls_sig;
+  const std::vector<int32_t>& cls_of = c->cls_of;
+  const std::vector<int32_t>& sig_rep = c->sig_rep;
+  const std::vector<int32_t>& rep = c->cls_fastrep;
+  const std::vector<int32_t>& slot_of = c->cls_slot;
+  int32_t* h_fill = stage_ints(c, p.o.fill);
+  int32_t* h_fchunks = stage_ints(c, p.o.fchunks);
+  int32_t* h_rep = stage_ints(c, p.o.rep);
+  int32_t* h_lrep = stage_ints(c, p.o.lrep);
+  const int ncls = int(c->cls_rep.size());
+  int nfchunks = 0, nruns = 0;
+  const int nsig = int(sig_rep.size());
+  std::vector<int32_t>& sig_base = c->sig_base;
+  sig_base.assign(size_t(nsig), -1);
+  {
+    std::vector<int32_t>& base_rep = c->base_rep;
+    base_rep.clear();
+    for (int g = 0; g < nsig; g++) {
+      const DevEval& e = hev[sig_rep[size_t(g)]];
+      for (size_t q = 0; q < base_rep.size() && sig_base[size_t(g)] < 0; q++)
+        if (keys.same_base(e, hev[base_rep[q]])) sig_base[size_t(g)] = int32_t(q);
+      if (sig_base[size_t(g)] < 0) {
+        sig_base[size_t(g)] = int32_t(base_rep.size());
+        base_rep.push_back(sig_rep[size_t(g)]);
+      }
+      if (base_rep.size() > 64) {  // many distinct bases (assumed usage per eval): no sharing to look for
+        for (int h = g + 1; h < nsig; h++) sig_base[size_t(h)] = int32_t(base_rep.size()) + (h - g - 1);
+        break;
+      }
+    }
+  }
+  std::vector<int32_t>& order = c->cls_order;
+  order.resize(size_t(ncls));
+  for (int k = 0; k < ncls; k++) order[size_t(k)] = k;
+  std::vector<int32_t>& sig_ncls = c->sig_ncls;  // classes per signature: small ones pack together
+  sig_ncls.assign(size_t(nsig), 0);
+  for (int k = 0; k < ncls; k++) sig_ncls[size_t(cls_sig[size_t(k)])]++;
+  auto small = [&](int32_t sg) { return sig_ncls[size_t(sg)] < kEvalsPerFillBlock / 2; };
+  std::stable_sort(order.begin(), order.end(), [&](int32_t k1, int32_t k2) {
+    const int32_t sa = cls_sig[size_t(k1)], sb = cls_sig[size_t(k2)];
+    const int32_t ba = sig_base[size_t(sa)], bb = sig_base[size_t(sb)];
+    if (ba != bb) return ba < bb;
+    if (small(sa) != small(sb)) return !small(sa);
+    return sa < sb;
+  });
+  trace(c, 7);
+  for (int k = 0; k < ncls; k++) h_fill[k] = rep[size_t(order[size_t(k)])];
+  p.nfill = ncls;
+  {  // members other than the rep, grouped by fill position (stats written by the reduce)
+    int32_t* h_moff = stage_ints(c, p.o.moff);
+    int32_t* h_mem = stage_ints(c, p.o.mem);
+    std::vector<int32_t>& pos = c->cls_pos;
+    pos.resize(size_t(ncls));
+    for (int k = 0; k < ncls; k++) pos[size_t(order[size_t(k)])] = k;
+    for (int k = 0; k <= ncls; k++) h_moff[k] = 0;
+    for (size_t i = 0; i < n; i++)
+      if (int32_t(i) != rep[size_t(cls_of[i])]) h_moff[pos[size_t(cls_of[i])] + 1]++;
+    for (int k = 0; k < ncls; k++) h_moff[k + 1] += h_moff[k];
+    std::vector<int32_t>& cur = c->cls_cur;
+    cur.assign(h_moff, h_moff + ncls);
+    for (size_t i = 0; i < n; i++)
+      if (int32_t(i) != rep[size_t(cls_of[i])]) h_mem[cur[size_t(pos[size_t(cls_of[i])])]++] = int32_t(i);
+  }
+  {  // counters are stored per class, row = fill position: evals and LFC tables refer to their class's row
+    const std::vector<int32_t>& pos = c->cls_pos;
+    for (size_t i = 0; i < n; i++) h_rep[i] = pos[size_t(cls_of[i])];
+    for (int k = 0; k < ncls; k++)
+      if (slot_of[size_t(k)] >= 0) h_lrep[slot_of[size_t(k)]] = pos[size_t(k)];
+  }
+  trace(c, 8);
+  int32_t* h_frun = stage_ints(c, p.o.frun);
+  // a signature with at least half a chunk of classes gets chunks of its
+  // own (one run: CountIn before the eval loop); the smaller ones of a base
+  // share packed chunks (several runs).  Single-run chunks first.
+  std::vector<int32_t>& packed = c->cls_packed;  // [start, len) signature runs left for packing
+  packed.clear();
+  for (int k = 0; k < ncls;) {
+    const int32_t sg = cls_sig[size_t(order[size_t(k)])];
+    int e = k + 1;
+    while (e < ncls && cls_sig[size_t(order[size_t(e)])] == sg) e++;
+    if (e - k >= kEvalsPerFillBlock / 2) {
+      for (int q = k; q < e; q += kEvalsPerFillBlock) {
+        h_fchunks[2 * nfchunks] = q;
+        h_fchunks[2 * nfchunks + 1] = std::min(kEvalsPerFillBlock, e - q);
+        nfchunks++;
+        for (int r = q; r < q + h_fchunks[2 * nfchunks - 1]; r++) h_frun[r] = nruns;
+        nruns++;
+      }
+    } else {
+      packed.push_back(k);
+      packed.push_back(e - k);
+    }
+    k = e;
+  }
+  p.nsingle = nfchunks;
+  for (size_t i = 0; i < packed.size();) {  // runs of one base, in order, up to a chunk each
+    const int32_t k0 = packed[i];
+    const int32_t base = sig_base[size_t(cls_sig[size_t(order[size_t(k0)])])];
+    int len = 0;
+    h_fchunks[2 * nfchunks] = k0;
+    while (i < packed.size() && len + packed[i + 1] <= kEvalsPerFillBlock && packed[i] == k0 + len &&
+           sig_base[size_t(cls_sig[size_t(order[size_t(packed[i])])])] == base) {
+      for (int r = packed[i]; r < packed[i] + packed[i + 1]; r++) h_frun[r] = nruns;
+      nruns++;
+      len += packed[i + 1];
+      i += 2;
+    }
+    h_fchunks[2 * nfchunks + 1] = len;
+    nfchunks++;
+  }
+  p.nfchunks = nfchunks;
+  p.nruns = nruns;
+}
+
+// Stage 7: every device buffer the chunk's kernels use, sized by the plan: the
+// class counter rows, the select slot groups and tag epoch, the result
+// buffers, the LFC tables and the leaf partials (and the chunk's record for
+// kueue_tas_last_counters).
+static int size_device_buffers(kueue_tas_ctx* c, const ChunkArgs& a, ChunkPlan& p) {
+  const DevSnap& s = c->snap;
+  const size_t n = a.n;
+  uint8_t* hs = c->h_stage.p;
+  const DevEval* hev = stage_evals(c, p);
+  const int32_t* h_fill = stage_ints(c, p.o.fill);
+  const int32_t* h_rep = stage_ints(c, p.o.rep);
+  const int32_t* h_bf = stage_ints(c, p.o.bf);
+  const int nfill = p.nfill, nbf = p.nbf, nslots = p.nslots;
   c->chunk_rep.assign(h_rep, h_rep + n);
   c->chunk_leader.resize(n);
   for (size_t i = 0; i < n; i++) c->chunk_leader[i] = (hev[i].flags & KUEUE_TAS_F_LEADER) ? 1 : 0;
-  c->chunk_alias.assign(n, 0);  // filled with the fill records below
-  // ---- device buffers ----
+  c->chunk_alias.assign(n, 0);  // filled with the fill records (build_fill_records)
   const int64_t SD = s.SD;
-  const int64_t full_lcap = int64_t(c->maxD) * 2 + 64;  // a list of any level's domains, twice
-  const int nchunks = (s.N + kLfcChunk - 1) / kLfcChunk;
+  const int64_t full_lcap = p.full_lcap = int64_t(c->maxD) * 2 + 64;
+  const int nchunks = p.nchunks = (s.N + kLfcChunk - 1) / kLfcChunk;
   {  // one row per class (fill position), sized by its kind (FillEvalParams::ctr_row)
     c->ctr_row_off.resize(size_t(std::max(nfill, 1)) + 1);
     int64_t at = 0;
@@ -2595,9 +2740,9 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
   // overlay, tags and scratch lists per BestFit-side select slot (fast-LFC
   // evals never mutate or walk lists): each slot's lists bounded by what its
   // walk can reach (scratch_bound), its overlay by its kind (2 fields, 5 with
-  // a leader); slots run in groups whose buffers fit phase2_budget, reusing
-  // one group's buffers (a fresh tag epoch per group)
-  SelSlot* hsel = reinterpret_cast<SelSlot*>(hs + o_sel);
+  // a leader); slots run in groups whose buffers fit Knobs::phase2_budget,
+  // reusing one group's buffers (a fresh tag epoch per group)
+  SelSlot* hsel = reinterpret_cast<SelSlot*>(hs + p.o.sel);
   std::vector<int32_t>& groups = c->sel_groups;
   groups.assign(1, 0);
   {
@@ -2605,10 +2750,10 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     int32_t g_tag = 0, max_tag = 1;
     for (int k = 0; k < nbf; k++) {
       const DevEval& ev = hev[h_bf[k]];
-      const int64_t lc = (c->scratch_full || !c->scratch_bounded) ? full_lcap : scratch_bound(c, s, ev, full_lcap);
+      const int64_t lc = (c->scratch_full || !c->knobs.scratch_bounded) ? full_lcap : scratch_bound(c, s, ev, full_lcap);
       const int64_t ovf = (ev.flags & KUEUE_TAS_F_LEADER) ? 5 : 2;
       const int64_t bytes = lc * 48 + (ovf + 1) * SD * 4;
-      if (g_tag > 0 && g_scr * 8 + g_ov * 4 + int64_t(g_tag) * SD * 4 + bytes > c->phase2_budget) {
+      if (g_tag > 0 && g_scr * 8 + g_ov * 4 + int64_t(g_tag) * SD * 4 + bytes > c->knobs.phase2_budget) {
         groups.push_back(k);
         g_scr = g_ov = 0;
         g_tag = 0;
@@ -2632,58 +2777,24 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     }
   }
   c->tag_epoch++;
-  const size_t nt = size_t(std::max(num_taints, 0));
-  const size_t stats_len = n * nt + n * size_t(s.R) + 3 * n;  // taints | resources | nodeSelector | affinity | topologyDomain
-  const size_t res_off_stats = (n * sizeof(kueue_tas_eval_out) + 15) / 16 * 16;
-  const size_t res_bytes = res_off_stats + stats_len * 4;
-  HIPCHK(c, c->d_res.ensure(res_bytes));
-  HIPCHK(c, c->h_res.ensure(res_bytes));
+  const size_t nt = size_t(std::max(a.num_taints, 0));
+  p.stats_len = n * nt + n * size_t(s.R) + 3 * n;  // taints | resources | nodeSelector | affinity | topologyDomain
+  p.res_off_stats = (n * sizeof(kueue_tas_eval_out) + 15) / 16 * 16;
+  p.res_bytes = p.res_off_stats + p.stats_len * 4;
+  HIPCHK(c, c->d_res.ensure(p.res_bytes));
+  HIPCHK(c, c->h_res.ensure(p.res_bytes));
   HIPCHK(c, c->h_res2.ensure(n));
-  kueue_tas_eval_out* d_out = reinterpret_cast<kueue_tas_eval_out*>(c->d_res.p);
-  int32_t* d_stats = reinterpret_cast<int32_t*>(c->d_res.p + res_off_stats);
   c->res_out_h = reinterpret_cast<kueue_tas_eval_out*>(c->h_res.p);
-  c->res_stats_h = reinterpret_cast<int32_t*>(c->h_res.p + res_off_stats);
+  c->res_stats_h = reinterpret_cast<int32_t*>(c->h_res.p + p.res_off_stats);
   // ExclusionStats are fully written by the fill's reduce (class reps) and the
   // replication (other members) when the staged fill counts them in LDS
-  uint32_t umask = 0;
-  for (size_t i = 0; i < n; i++) umask |= hev[i].req_mask | hev[i].lead_mask;
-  const int ucols = __builtin_popcount(umask);
-  const int nstat_all = kStatFixed + int(nt) + s.R;
-  const bool lds_stats = s.N > 0 && nfchunks > 0 && ucols <= 8 && nstat_all <= kMaxFillStats;
-  // per-eval entry regions [n][entry_cap] pairs in pinned, device-mapped host
-  // memory: select / lfc_emit write the (leaf, count) pairs the host reads
-  // after the batch's one sync (no offsets/pack kernels, no entries D2H)
-  {
-    const size_t need_ints = c->ent_used + size_t(n) * size_t(entry_cap) * 2;
-    if (need_ints > c->ent_cap) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      size_t cap = std::max<size_t>(need_ints, 2 * c->ent_cap);
-      int32_t* p = nullptr;
-      HIPCHK(c, hipHostMalloc(&p, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
-      if (c->ent_used) memcpy(p, c->ent_host, c->ent_used * 4);
-      if (c->ent_host) (void)hipHostFree(c->ent_host);
-      c->ent_host = p;
-      c->ent_cap = cap;
-      HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->ent_dev), p, 0));
-    }
-    if (c->leaf_tags_on && c->tag_cap < c->ent_cap / 2) {  // one tag per entry pair, same layout
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      const size_t cap = c->ent_cap / 2;
-      uint64_t* p = nullptr;
-      HIPCHK(c, hipHostMalloc(&p, cap * 8, hipHostMallocMapped | hipHostMallocCoherent));
-      if (c->ent_used && c->tag_host) memcpy(p, c->tag_host, c->ent_used / 2 * 8);
-      if (c->tag_host) (void)hipHostFree(c->tag_host);
-      c->tag_host = p;
-      c->tag_cap = cap;
-      HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->tag_dev), p, 0));
-    }
-    if (c->leaf_tags_on) c->fill_paths |= KUEUE_TAS_PATH_ENTRY_TAGS;
-    c->snap.leaf_tag = c->leaf_tags_on ? c->d_leaf_tags.p : nullptr;
-    c->snap.tag_out = c->leaf_tags_on ? c->tag_dev : nullptr;
-    c->snap.ent_base = c->ent_dev;
-  }
+  p.umask = 0;
+  for (size_t i = 0; i < n; i++) p.umask |= hev[i].req_mask | hev[i].lead_mask;
+  p.ucols = __builtin_popcount(p.umask);
+  p.nstat_all = kStatFixed + int(nt) + s.R;
+  p.lds_stats = s.N > 0 && p.nfchunks > 0 && p.ucols <= 8 && p.nstat_all <= kMaxFillStats;
   HIPCHK(c, c->d_lfc_jobs.ensure(n));
-  HIPCHK(c, c->d_lfc_items.ensure(size_t(std::max(nfast, 1)) * size_t(std::max(nchunks, 1)) + 1));
+  HIPCHK(c, c->d_lfc_items.ensure(size_t(std::max(p.nfast, 1)) * size_t(std::max(nchunks, 1)) + 1));
   // chunk counts and overflow sums in two halves used by alternate batches:
   // the fill accumulates into zeroed tables (DevBatch::lfc_fill), and a
   // half's zeroing runs on stream2 during the batch that does not use it
@@ -2694,139 +2805,203 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     HIPCHK(c, c->d_lfc_ovs.ensure(2 * c->lfc_half));
     c->lfc_dirty[0] = c->lfc_dirty[1] = true;
   }
-  const int lfc_cur = c->lfc_parity;
+  p.lfc_cur = c->lfc_parity;
   HIPCHK(c, c->d_lfc_cp.ensure(size_t(std::max(nslots * nchunks, 1)) * kLfcBins));
   HIPCHK(c, c->d_lfc_tot.ensure(size_t(std::max(nslots, 1)) * kLfcBins));
-
   HIPCHK(c, c->d_lfc_ovtot.ensure(size_t(std::max(nslots, 1))));
   HIPCHK(c, c->d_lfc_u8.ensure(size_t(std::max(nslots, 1)) * size_t(std::max(nchunks, 1)) * kLfcChunk));
-  const int nblk = (s.N + 255) / 256 * 4;  // one leaf partial per 64-leaf wave
-  HIPCHK(c, c->d_partials.ensure(size_t(std::max(nleafsel, 1)) * size_t(std::max(nblk, 1))));
-
+  p.nblk = (s.N + 255) / 256 * 4;
+  HIPCHK(c, c->d_partials.ensure(size_t(std::max(p.nleafsel, 1)) * size_t(std::max(p.nblk, 1))));
   if (c->fused_top) {  // rollup_top_kernel's initial level maxima and arrival counters
-    int32_t* t = reinterpret_cast<int32_t*>(hs + o_top);
+    int32_t* t = stage_ints(c, p.o.top);
     for (size_t i = 0; i < size_t(nfill) * kMaxLevels; i++) t[i] = INT32_MIN;
     for (size_t i = 0; i < size_t(nfill); i++) t[n * kMaxLevels + i] = 0;
   }
-  trace(10);
-  // fill_pair_kernel's per-position records in fill order (FillPos)
-  {
-    FillPos* fp = reinterpret_cast<FillPos*>(hs + o_fpos);
-    const int32_t* h_fill = reinterpret_cast<const int32_t*>(hs + o_fill);
-    const int32_t* h_fch = reinterpret_cast<const int32_t*>(hs + o_fchunks);
-    const int32_t* h_frun = reinterpret_cast<const int32_t*>(hs + o_frun);
-    const int nsw = ucols <= 4 ? 4 : ucols <= 5 ? 5 : 8;  // the launch's NS: worker terms [0, NS), leader terms [NS, 2 NS)
-    for (int ch = 0; ch < nfchunks; ch++) {
-      const int e0 = h_fch[2 * ch], ne = h_fch[2 * ch + 1];
-      const DevEval& base = hev[h_fill[e0]];
-      for (int t = 0; t < ne; t++) {
-        const int pos = e0 + t;
-        const DevEval& ev = hev[h_fill[pos]];
-        FillPos& r = fp[pos];
-        memset(&r, 0, sizeof r);
-        FillEvalParams& P = r.p;
-        P.eid = h_fill[pos];
-        P.lfc_slot = c->cls_slot[size_t(c->cls_order[size_t(pos)])];  // fast-LFC table slot, -1: none
-        P.taint_off = ev.taint_table;
-        P.nsel = ev.nsel;
-        P.slice_size = ev.slice_size;
-        P.slice_level = ev.slice_level;
-        P.inner = ev.ssal[s.L - 1];
-        const bool aff = (ev.flags & KUEUE_TAS_F_AFFINITY) != 0;
-        P.aff_begin = aff ? ev.aff_begin : -1;
-        P.aff_end = aff ? ev.aff_end : -1;
-        P.dom_begin = ev.dom_begin;
-        P.dom_end = ev.dom_end;
-        for (int k = 0; k < KUEUE_TAS_MAX_SELECTORS; k++) {
-          P.sel_col[k] = ev.sel_col[k];
-          P.sel_val[k] = ev.sel_val[k];
-          if (k < ev.nsel && ev.sel_col[k] >= kStagedLabels) P.sel_far = 1;
-        }
-        P.sx_begin = ev.sx_begin;
-        P.sx_end = ev.sx_end;
-        P.ss_alias = simple_class(ev, s.L) ? 1 : 0;
-        P.ctr_row = c->ctr_row_off[size_t(pos)];
-        if (ev.sx_begin >= 0) P.sel_far = 1;
-        {  // the packed nodeSelector compare (FillEvalParams::sel_fast)
-          uint32_t m[2] = {0u, 0u}, w[2] = {0u, 0u};
-          bool fast = c->labels16 && !P.sel_far, never = false;
-          for (int k = 0; k < ev.nsel && fast; k++) {
-            const int col = ev.sel_col[k];
-            const uint32_t sh = uint32_t(col & 1) * 16u;
-            const uint32_t fm = 0xffffu << sh;
-            if (col < 0 || col >= kStagedLabels) {
-              fast = false;
-              break;
-            }
-            const int32_t val = ev.sel_val[k];
-            if (val < 0 || val > 0xffff) {  // a value no leaf has
-              never = true;
-              continue;
-            }
-            const uint32_t fw = uint32_t(val) << sh;
-            uint32_t& mm = m[col >> 1];
-            uint32_t& ww = w[col >> 1];
-            if ((mm & fm) && (ww & fm) != fw) never = true;  // one column, two values
-            mm |= fm;
-            ww = (ww & ~fm) | fw;
-          }
-          if (fast && never) {  // want bits outside the mask: no leaf matches
-            m[0] = 0u;
-            w[0] = 1u;
-          }
-          P.sel_fast = fast ? 1 : 0;
-          P.sel_mlo = m[0];
-          P.sel_mhi = m[1];
-          P.sel_wlo = w[0];
-          P.sel_whi = w[1];
-        }
-        P.run = h_frun[pos];
-        P.sig_new = t == 0 || h_frun[pos - 1] != P.run;
-        P.rmask = int32_t(ev.req_mask);
-        P.lmask = int32_t(ev.lead_mask);
-        P.pad[0] = int32_t(base.flags);  // the chunk's base signature
-        P.pad[1] = base.assumed_begin;
-        P.pad[2] = base.assumed_end;
-        for (int q = 0; q < kStagedProfiles; q++)
-          r.taint[q] = q < c->num_profiles && size_t(ev.taint_table + q) < taint_table_len ? taint_table[ev.taint_table + q] : -1;
-        for (int j = 0; j < ev.nreq && j < nsw; j++) r.term[j] = hterms[ev.term_begin + j];
-        for (int j = 0; j < ev.nlead && j < nsw; j++) r.term[nsw + j] = hterms[ev.lead_begin + j];
-      }
-    }
-    for (size_t i = 0; i < n; i++) c->chunk_alias[i] = uint8_t(fp[c->chunk_rep[i]].p.ss_alias);
-    for (int k = 0; k < nfill; k++) c->last_alias_fills += fp[k].p.ss_alias;
+  return KUEUE_TAS_OK;
+}
+
+// Stage 8: the per-eval entry regions [n][entry_cap] (leaf, count) pairs in
+// pinned, device-mapped host memory: select / lfc_emit write the pairs the
+// host reads after the batch's one sync (no offsets/pack kernels, no entries
+// D2H); with leaf tags on, one tag per pair in a region of the same layout.
+//
+// Invariants, in int32 units of ent_host (a pair is two) and uint64 units of
+// tag_host (one per pair), with n regions of entry_cap pairs claimed by this
+// chunk (claim_entry_regions adds them to ent_used once the chunk is kept):
+//   ent_used + n * entry_cap * 2 <= ent_cap
+//   (ent_used + n * entry_cap * 2) / 2 <= tag_cap   (tag_cap >= ent_cap / 2)
+// A region that grows keeps the batch's earlier chunks' pairs ([0, ent_used)).
+static int ensure_entry_regions(kueue_tas_ctx* c, const ChunkArgs& a) {
+  const size_t need_ints = c->ent_used + a.n * size_t(c->entry_cap) * 2;
+  if (need_ints > c->ent_cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t cap = std::max<size_t>(need_ints, 2 * c->ent_cap);
+    int32_t* q = nullptr;
+    HIPCHK(c, hipHostMalloc(&q, cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
+    if (c->ent_used) memcpy(q, c->ent_host, c->ent_used * 4);
+    if (c->ent_host) (void)hipHostFree(c->ent_host);
+    c->ent_host = q;
+    c->ent_cap = cap;
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->ent_dev), q, 0));
   }
-  trace(11);
+  if (c->leaf_tags_on && c->tag_cap < c->ent_cap / 2) {  // one tag per entry pair, same layout
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t cap = c->ent_cap / 2;
+    uint64_t* q = nullptr;
+    HIPCHK(c, hipHostMalloc(&q, cap * 8, hipHostMallocMapped | hipHostMallocCoherent));
+    if (c->ent_used && c->tag_host) memcpy(q, c->tag_host, c->ent_used / 2 * 8);
+    if (c->tag_host) (void)hipHostFree(c->tag_host);
+    c->tag_host = q;
+    c->tag_cap = cap;
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->tag_dev), q, 0));
+  }
+  if (c->leaf_tags_on) c->fill_paths |= KUEUE_TAS_PATH_ENTRY_TAGS;
+  c->snap.leaf_tag = c->leaf_tags_on ? c->d_leaf_tags.p : nullptr;
+  c->snap.tag_out = c->leaf_tags_on ? c->tag_dev : nullptr;
+  c->snap.ent_base = c->ent_dev;
+  return KUEUE_TAS_OK;
+}
+
+// Stage 9: fill_pair_kernel's per-position records in fill order (FillPos),
+// with the packed nodeSelector compare; chunk_alias and last_alias_fills.
+static void build_fill_records(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p) {
+  const DevSnap& s = c->snap;
+  const size_t n = a.n;
+  const int32_t* taint_table = a.taint_table;
+  const size_t taint_table_len = a.taint_table_len;
+  const DevEval* hev = stage_evals(c, p);
+  const DevTerm* hterms = stage_terms(c, p);
+  const int ucols = p.ucols, nfchunks = p.nfchunks, nfill = p.nfill;
+  FillPos* fp = reinterpret_cast<FillPos*>(c->h_stage.p + p.o.fpos);
+  const int32_t* h_fill = stage_ints(c, p.o.fill);
+  const int32_t* h_fch = stage_ints(c, p.o.fchunks);
+  const int32_t* h_frun = stage_ints(c, p.o.frun);
+  const int nsw = ucols <= 4 ? 4 : ucols <= 5 ? 5 : 8;  // the launch's NS: worker terms [0, NS), leader terms [NS, 2 NS)
+  for (int ch = 0; ch < nfchunks; ch++) {
+    const int e0 = h_fch[2 * ch], ne = h_fch[2 * ch + 1];
+    const DevEval& base = hev[h_fill[e0]];
+    for (int t = 0; t < ne; t++) {
+      const int pos = e0 + t;
+      const DevEval& ev = hev[h_fill[pos]];
+      FillPos& r = fp[pos];
+      memset(&r, 0, sizeof r);
+      FillEvalParams& P = r.p;
+      P.eid = h_fill[pos];
+      P.lfc_slot = c->cls_slot[size_t(c->cls_order[size_t(pos)])];  // fast-LFC table slot, -1: none
+      P.taint_off = ev.taint_table;
+      P.nsel = ev.nsel;
+      P.slice_size = ev.slice_size;
+      P.slice_level = ev.slice_level;
+      P.inner = ev.ssal[s.L - 1];
+      const bool aff = (ev.flags & KUEUE_TAS_F_AFFINITY) != 0;
+      P.aff_begin = aff ? ev.aff_begin : -1;
+      P.aff_end = aff ? ev.aff_end : -1;
+      P.dom_begin = ev.dom_begin;
+      P.dom_end = ev.dom_end;
+      for (int k = 0; k < KUEUE_TAS_MAX_SELECTORS; k++) {
+        P.sel_col[k] = ev.sel_col[k];
+        P.sel_val[k] = ev.sel_val[k];
+        if (k < ev.nsel && ev.sel_col[k] >= kStagedLabels) P.sel_far = 1;
+      }
+      P.sx_begin = ev.sx_begin;
+      P.sx_end = ev.sx_end;
+      P.ss_alias = simple_class(ev, s.L) ? 1 : 0;
+      P.ctr_row = c->ctr_row_off[size_t(pos)];
+      if (ev.sx_begin >= 0) P.sel_far = 1;
+      {  // the packed nodeSelector compare (FillEvalParams::sel_fast)
+        uint32_t m[2] = {0u, 0u}, w[2] = {0u, 0u};
+        bool fast = c->labels16 && !P.sel_far, never = false;
+        for (int k = 0; k < ev.nsel && fast; k++) {
+          const int col = ev.sel_col[k];
+          const uint32_t sh = uint32_t(col & 1) * 16u;
+          const uint32_t fm = 0xffffu << sh;
+          if (col < 0 || col >= kStagedLabels) {
+            fast = false;
+            break;
+          }
+          const int32_t val = ev.sel_val[k];
+          if (val < 0 || val > 0xffff) {  // a value no leaf has
+            never = true;
+            continue;
+          }
+          const uint32_t fw = uint32_t(val) << sh;
+          uint32_t& mm = m[col >> 1];
+          uint32_t& ww = w[col >> 1];
+          if ((mm & fm) && (ww & fm) != fw) never = true;  // one column, two values
+          mm |= fm;
+          ww = (ww & ~fm) | fw;
+        }
+        if (fast && never) {  // want bits outside the mask: no leaf matches
+          m[0] = 0u;
+          w[0] = 1u;
+        }
+        P.sel_fast = fast ? 1 : 0;
+        P.sel_mlo = m[0];
+        P.sel_mhi = m[1];
+        P.sel_wlo = w[0];
+        P.sel_whi = w[1];
+      }
+      P.run = h_frun[pos];
+      P.sig_new = t == 0 || h_frun[pos - 1] != P.run;
+      P.rmask = int32_t(ev.req_mask);
+      P.lmask = int32_t(ev.lead_mask);
+      P.pad[0] = int32_t(base.flags);  // the chunk's base signature
+      P.pad[1] = base.assumed_begin;
+      P.pad[2] = base.assumed_end;
+      for (int q = 0; q < kStagedProfiles; q++)
+        r.taint[q] = q < c->num_profiles && size_t(ev.taint_table + q) < taint_table_len ? taint_table[ev.taint_table + q] : -1;
+      for (int j = 0; j < ev.nreq && j < nsw; j++) r.term[j] = hterms[ev.term_begin + j];
+      for (int j = 0; j < ev.nlead && j < nsw; j++) r.term[nsw + j] = hterms[ev.lead_begin + j];
+    }
+  }
+  for (size_t i = 0; i < n; i++) c->chunk_alias[i] = uint8_t(fp[c->chunk_rep[i]].p.ss_alias);
+  for (int k = 0; k < nfill; k++) c->last_alias_fills += fp[k].p.ss_alias;
+}
+
+// g_select_snap is one per device: batches of different contexts must not
+// interleave (kueue_tas_eval_batch_ptrs holds the mutex for the whole batch).
+// It also guards the cache below: what each device's g_select_snap holds.
+static std::mutex select_snap_mu;
+static DevSnap select_snap_uploaded[16];
+static bool select_snap_valid[16];
+
+// Stage 10: the arena's one H2D copy, the select path's descriptor, and the
+// kernels' batch descriptor (DevBatch).  Trace point 12 (upload) lies inside.
+static int upload_and_describe(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p, DevBatch& b) {
+  const DevSnap& s = c->snap;
+  const size_t n = a.n;
+  const ArenaOffsets& o = p.o;
   if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_stage.p, hs, o_fpos + size_t(nfill) * sizeof(FillPos), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_stage.p, c->h_stage.p, o.fpos + size_t(p.nfill) * sizeof(FillPos), hipMemcpyHostToDevice,
+                           c->stream));
   // the select path's descriptor (g_select_snap), ordered before both select
   // launches: stream2 joins after events recorded later on this stream.
   // Uploaded only when it differs from what the device already holds (the
   // caller serializes batches per process, and every batch drains before
   // eval_batch returns), so a steady stream of batches pays no extra copy.
   {
-    static DevSnap uploaded[16];
-    static bool valid[16];
     const int dev = (c->device >= 0 && c->device < 16) ? c->device : -1;
-    if (dev < 0 || !valid[dev] || std::memcmp(&uploaded[dev], &c->snap, sizeof(DevSnap)) != 0) {
+    if (dev < 0 || !select_snap_valid[dev] || std::memcmp(&select_snap_uploaded[dev], &c->snap, sizeof(DevSnap)) != 0) {
       HIPCHK(c, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_select_snap), &c->snap, sizeof(DevSnap), 0,
                                        hipMemcpyHostToDevice, c->stream));
       if (dev >= 0) {
-        std::memcpy(&uploaded[dev], &c->snap, sizeof(DevSnap));
-        valid[dev] = true;
+        std::memcpy(&select_snap_uploaded[dev], &c->snap, sizeof(DevSnap));
+        select_snap_valid[dev] = true;
       }
     }
   }
-  trace(12);
-  if (!lds_stats) HIPCHK(c, hipMemsetAsync(d_stats, 0, stats_len * 4, c->stream));
+  trace(c, 12);
+  const size_t nt = size_t(std::max(a.num_taints, 0));
+  kueue_tas_eval_out* d_out = reinterpret_cast<kueue_tas_eval_out*>(c->d_res.p);
+  int32_t* d_stats = reinterpret_cast<int32_t*>(c->d_res.p + p.res_off_stats);
+  if (!p.lds_stats) HIPCHK(c, hipMemsetAsync(d_stats, 0, p.stats_len * 4, c->stream));
   uint8_t* ds = c->d_stage.p;
-  DevBatch b{};
-  b.evals = reinterpret_cast<const DevEval*>(ds + o_evals);
-  b.terms = reinterpret_cast<const DevTerm*>(ds + o_terms);
-  b.taint_table = reinterpret_cast<const int32_t*>(ds + o_taint);
-  b.assumed = reinterpret_cast<const kueue_tas_assumed*>(ds + o_assumed);
-  b.aff = reinterpret_cast<const kueue_tas_affinity_req*>(ds + o_aff);
-  b.aff_vals = reinterpret_cast<const int32_t*>(ds + o_affv);
+  b.evals = reinterpret_cast<const DevEval*>(ds + o.evals);
+  b.terms = reinterpret_cast<const DevTerm*>(ds + o.terms);
+  b.taint_table = reinterpret_cast<const int32_t*>(ds + o.taint);
+  b.assumed = reinterpret_cast<const kueue_tas_assumed*>(ds + o.assumed);
+  b.aff = reinterpret_cast<const kueue_tas_affinity_req*>(ds + o.aff);
+  b.aff_vals = reinterpret_cast<const int32_t*>(ds + o.affv);
   b.n = int32_t(n);
   b.num_taints = int32_t(nt);
   b.num_profiles = c->num_profiles;
@@ -2839,7 +3014,7 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
   b.cls_members = nullptr;
   b.rack_fanout = 0;
   b.rack_pos = nullptr;
-  b.ctr_sd = SD;
+  b.ctr_sd = s.SD;
   b.counters = c->d_counters.p;
   b.overlay = c->d_overlay.p;
   b.tags = c->d_tags.p;
@@ -2851,25 +3026,25 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
   b.dom_counts = b.aff_counts + n;
   b.out = d_out;
   b.entries = c->ent_dev + c->ent_used;
-  b.entry_cap = entry_cap;
-  b.sel_slots = reinterpret_cast<const SelSlot*>(ds + o_sel);
+  b.entry_cap = c->entry_cap;
+  b.sel_slots = reinterpret_cast<const SelSlot*>(ds + o.sel);
   b.slot_base = 0;
   b.scratch = c->d_scratch.p;
   b.list_cap = c->list_cap;
-  b.nblk = nblk;
+  b.nblk = p.nblk;
   b.partials = c->d_partials.p;
-  b.partial_idx = reinterpret_cast<const int32_t*>(ds + o_pidx);
-  b.rep_of = reinterpret_cast<const int32_t*>(ds + o_rep);
-  b.lfc_slot = reinterpret_cast<const int32_t*>(ds + o_slot);
-  b.lfc_rep = reinterpret_cast<const int32_t*>(ds + o_lrep);
-  b.lfc_nslots = nslots;
-  b.lfc_nchunks = nchunks;
-  b.lfc_ch = c->d_lfc_ch.p + size_t(lfc_cur) * c->lfc_half * kLfcBins;
+  b.partial_idx = reinterpret_cast<const int32_t*>(ds + o.pidx);
+  b.rep_of = reinterpret_cast<const int32_t*>(ds + o.rep);
+  b.lfc_slot = reinterpret_cast<const int32_t*>(ds + o.slot);
+  b.lfc_rep = reinterpret_cast<const int32_t*>(ds + o.lrep);
+  b.lfc_nslots = p.nslots;
+  b.lfc_nchunks = p.nchunks;
+  b.lfc_ch = c->d_lfc_ch.p + size_t(p.lfc_cur) * c->lfc_half * kLfcBins;
   b.lfc_u8 = c->d_lfc_u8.p;
-  b.exp_flags = c->exp_flags;
+  b.exp_flags = c->knobs.exp_flags;
   b.lfc_cp = c->d_lfc_cp.p;
   b.lfc_tot = c->d_lfc_tot.p;
-  b.lfc_ovs = c->d_lfc_ovs.p + size_t(lfc_cur) * c->lfc_half;
+  b.lfc_ovs = c->d_lfc_ovs.p + size_t(p.lfc_cur) * c->lfc_half;
   b.lfc_ovtot = c->d_lfc_ovtot.p;
   b.lfc_jobs = c->d_lfc_jobs.p;
   b.lfc_nitems = reinterpret_cast<int32_t*>(c->d_lfc_items.p);  // item 0's slot holds the count
@@ -2883,30 +3058,136 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     HIPCHK(c, hipMemsetAsync(c->d_fprof.p, 0, (size_t(1) << 18) * 4, c->stream));
     b.fill_prof = c->d_fprof.p;
   }
-  c->stat_fills += nfill;
+  c->stat_fills += p.nfill;
   c->stat_evals += int64_t(n);
-  const int32_t* d_pairs = reinterpret_cast<const int32_t*>(ds + o_pairs);
-  const int32_t* d_leafsel = reinterpret_cast<const int32_t*>(ds + o_leafsel);
-  b.fill_ids = reinterpret_cast<const int32_t*>(ds + o_fill);
-  b.nfill = nfill;
-  b.fill_chunks = reinterpret_cast<const int32_t*>(ds + o_fchunks);
-  b.fill_run = reinterpret_cast<const int32_t*>(ds + o_frun);
-  b.fill_pos = reinterpret_cast<const FillPos*>(ds + o_fpos);
-  // K1
+  b.fill_ids = reinterpret_cast<const int32_t*>(ds + o.fill);
+  b.nfill = p.nfill;
+  b.fill_chunks = reinterpret_cast<const int32_t*>(ds + o.fchunks);
+  b.fill_run = reinterpret_cast<const int32_t*>(ds + o.frun);
+  b.fill_pos = reinterpret_cast<const FillPos*>(ds + o.fpos);
+  return KUEUE_TAS_OK;
+}
+
+// ---- The fill launch.  The instantiated kernels, all of them:
+//   fill_pair_kernel<NS, TS, MR, GL, FC>                     NS 4|5|8; TS, MR, GL either; FC -1|0|32
+//   fill_pair_kernel<NS, true, false, false, FC, true, LF>   leaf categories: NS 4|5|8; FC -1|0|32; LF either
+//   fill_leaves_staged_kernel<NS, TS, MR, GL>                NS 4|5|8; TS, MR, GL either
+//   fill_leaves_kernel<MAXT>                                 MAXT 4|8|16|32
+// NS: the staged snapshot columns (ucols <= 4, <= 5, <= 8); TS: taint rows in
+// LDS (FillLaunch::ts); MR: multi-run chunks; GL: global lookups in the eval
+// loop (FillLaunch::gl); FC: -1 ragged pair, 32 for a rack fan-out of 32, else
+// 0; LF: DevBatch::lfc_fill.  Every launch names its kernel: a runtime flag
+// becomes a template argument only where the table has both values. ----
+extern "C++" {
+
+// chunks [first, first + count) of one kind (MR: multi-run) in one launch on `st`
+template <int NS, bool TS, bool MR>
+static void launch_fill_chunks(kueue_tas_ctx* c, const FillLaunch& f, const DevBatch& b, uint32_t umask, int first,
+                               int count, hipStream_t st) {
+  if (count <= 0) return;
+  const DevSnap& s = c->snap;
+  if (!f.pair) {
+    const dim3 sg(f.sgx, unsigned(count));
+    if (f.gl) hipLaunchKernelGGL((fill_leaves_staged_kernel<NS, TS, MR, true>), sg, dim3(256), 0, st, s, b, umask, first);
+    else hipLaunchKernelGGL((fill_leaves_staged_kernel<NS, TS, MR, false>), sg, dim3(256), 0, st, s, b, umask, first);
+    return;
+  }
+  c->fill_paths |= KUEUE_TAS_PATH_PAIR;  // kPairLP leaves per thread
+  const dim3 pg(f.pgx, unsigned(count));
+  const int fc = f.ragged_pair ? -1 : b.rack_fanout == 32 ? 32 : 0;
+#define KTAS_LAUNCH_PAIR(GL, FC) \
+  hipLaunchKernelGGL((fill_pair_kernel<NS, TS, MR, GL, FC>), pg, dim3(256), 0, st, s, b, umask, first)
+#define KTAS_LAUNCH_CAT(FC, LF) \
+  hipLaunchKernelGGL((fill_pair_kernel<NS, true, false, false, FC, true, LF>), pg, dim3(256), 0, st, s, b, umask, first)
+  if constexpr (TS && !MR) {  // single-run chunks: leaf categories
+    if (f.cat) {
+      c->fill_paths |= KUEUE_TAS_PATH_CATEGORY;
+      if (b.lfc_fill) {  // (the lean loop's LFC pair lists in LDS)
+        if (fc < 0) KTAS_LAUNCH_CAT(-1, true);
+        else if (fc == 32) KTAS_LAUNCH_CAT(32, true);
+        else KTAS_LAUNCH_CAT(0, true);
+      } else if (fc < 0) {
+        KTAS_LAUNCH_CAT(-1, false);
+      } else if (fc == 32) {
+        KTAS_LAUNCH_CAT(32, false);
+      } else {
+        KTAS_LAUNCH_CAT(0, false);
+      }
+      return;
+    }
+  }
+  if (f.gl) {
+    if (fc < 0) KTAS_LAUNCH_PAIR(true, -1);
+    else if (fc == 32) KTAS_LAUNCH_PAIR(true, 32);
+    else KTAS_LAUNCH_PAIR(true, 0);
+  } else if (fc < 0) {
+    KTAS_LAUNCH_PAIR(false, -1);
+  } else if (fc == 32) {
+    KTAS_LAUNCH_PAIR(false, 32);
+  } else {
+    KTAS_LAUNCH_PAIR(false, 0);
+  }
+#undef KTAS_LAUNCH_PAIR
+#undef KTAS_LAUNCH_CAT
+}
+
+// single-run chunks [0, nsingle) and multi-run chunks [nsingle, nfchunks): one
+// launch each.  The multi-run chunks (a few small signatures) run beside the
+// single-run chunks on stream2 (idle until the fill is done): their launch's
+// ramp and tail overlap the big launch instead of following it
+template <int NS, bool TS>
+static int launch_staged_fill(kueue_tas_ctx* c, const ChunkPlan& p, const FillLaunch& f, const DevBatch& b) {
+  const int nsingle = p.nsingle, nmulti = p.nfchunks - p.nsingle;
+  const bool side = nsingle > 0 && nmulti > 0;
+  if (side) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[1], 0));
+    launch_fill_chunks<NS, TS, true>(c, f, b, p.umask, nsingle, nmulti, c->stream2);
+    HIPCHK(c, hipEventRecord(c->evl[2], c->stream2));
+  } else {
+    launch_fill_chunks<NS, TS, true>(c, f, b, p.umask, nsingle, nmulti, c->stream);
+  }
+  launch_fill_chunks<NS, TS, false>(c, f, b, p.umask, 0, nsingle, c->stream);
+  if (side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evl[2], 0));
+  return KUEUE_TAS_OK;
+}
+
+}  // extern "C++"
+
+static int launch_fill(kueue_tas_ctx* c, const ChunkPlan& p, const FillLaunch& f, const DevBatch& b, dim3 grid) {
+  const DevSnap& s = c->snap;
+  if (p.ucols <= 4) return f.ts ? launch_staged_fill<4, true>(c, p, f, b) : launch_staged_fill<4, false>(c, p, f, b);
+  if (p.ucols <= 5) return f.ts ? launch_staged_fill<5, true>(c, p, f, b) : launch_staged_fill<5, false>(c, p, f, b);
+  if (p.ucols <= 8) return f.ts ? launch_staged_fill<8, true>(c, p, f, b) : launch_staged_fill<8, false>(c, p, f, b);
+  // more than 8 columns: the generic kernel, terms from global memory
+  if (p.maxt <= 4) hipLaunchKernelGGL(fill_leaves_kernel<4>, grid, dim3(256), 0, c->stream, s, b);
+  else if (p.maxt <= 8) hipLaunchKernelGGL(fill_leaves_kernel<8>, grid, dim3(256), 0, c->stream, s, b);
+  else if (p.maxt <= 16) hipLaunchKernelGGL(fill_leaves_kernel<16>, grid, dim3(256), 0, c->stream, s, b);
+  else hipLaunchKernelGGL(fill_leaves_kernel<32>, grid, dim3(256), 0, c->stream, s, b);
+  return KUEUE_TAS_OK;
+}
+
+// Stage 11 (K1): the fill: the path decision (FillLaunch, the KUEUE_TAS_PATH_*
+// bits), the buffers only some paths need, and the launches.
+static int enqueue_fill(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p, DevBatch& b) {
+  const DevSnap& s = c->snap;
+  const size_t n = a.n;
+  const DevEval* hev = stage_evals(c, p);
+  const int nfill = p.nfill, nfchunks = p.nfchunks, ucols = p.ucols;
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   c->last_stats[0] += nfill;
   if (s.N > 0 && nfchunks > 0) {
-    dim3 grid((s.N + 255) / 256, unsigned(nfchunks));
+    FillLaunch f;
+    const dim3 grid((s.N + 255) / 256, unsigned(nfchunks));
     // the staged kernels take kFillTilesPerBlock leaf tiles per block (with
     // ragged parents a tile is 4 packed wave slots)
-    const bool staged_fill = ucols <= 8;
+    f.staged_fill = ucols <= 8;
     const unsigned stiles = ucols <= 8 && c->rack_fanout < 0 ? unsigned((s.n_wave_slots + 3) / 4) : grid.x;
-    const unsigned sgx = (stiles + kFillTilesPerBlock - 1) / kFillTilesPerBlock;
-    const unsigned nblk_fill = staged_fill ? sgx : grid.x;  // blocks per fill position (stats partials)
+    f.sgx = (stiles + kFillTilesPerBlock - 1) / kFillTilesPerBlock;
+    f.nblk_fill = f.staged_fill ? f.sgx : grid.x;
     c->last_stats[2] += 1;
     c->last_stats[3] = ucols;
-    const int nstat = nstat_all;
-    b.nstat = lds_stats ? nstat : 0;
+    const int nstat = p.nstat_all;
+    b.nstat = p.lds_stats ? nstat : 0;
     b.nstat_R = s.R;
     // single-run chunks on fill_pair_kernel (kPairLP leaves per thread): staged
     // columns, uniform fan-out >= 2 or no fused parents; it counts the
@@ -2916,47 +3197,46 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     // leader (leader classes keep the one-leaf staged kernel)
     bool any_leader = false;
     for (size_t i = 0; i < n && !any_leader; i++) any_leader = (hev[i].flags & KUEUE_TAS_F_LEADER) != 0;
-    const bool ragged_pair = c->pair_fill && staged_fill && s.wave_tab2 != nullptr && !any_leader;
-    const bool pair = c->pair_fill && staged_fill &&
-                      (ragged_pair || (c->rack_fanout >= 0 && (c->rack_fanout == 0 || c->rack_fanout >= kPairLP)));
-    const unsigned pgx = ragged_pair ? unsigned((s.n_wave_slots2 + 3) / 4) : unsigned((s.N + kPairTile - 1) / kPairTile);
+    f.ragged_pair = c->pair_fill && f.staged_fill && s.wave_tab2 != nullptr && !any_leader;
+    f.pair = c->pair_fill && f.staged_fill &&
+             (f.ragged_pair || (c->rack_fanout >= 0 && (c->rack_fanout == 0 || c->rack_fanout >= kPairLP)));
+    f.pgx = f.ragged_pair ? unsigned((s.n_wave_slots2 + 3) / 4) : unsigned((s.N + kPairTile - 1) / kPairTile);
     if (b.nstat) {
       // sized for the tile grid: fill_exclusion_kernel (split stats) writes one partial per tile
-      HIPCHK(c, c->d_fill_stats.ensure(size_t(nfill) * std::max(grid.x, nblk_fill) * size_t(nstat)));
+      HIPCHK(c, c->d_fill_stats.ensure(size_t(nfill) * std::max(grid.x, f.nblk_fill) * size_t(nstat)));
       b.fill_stats = c->d_fill_stats.p;
       // the reduce sums every member's stats and stores them for the class's other members
-      b.cls_member_off = reinterpret_cast<const int32_t*>(ds + o_moff);
-      b.cls_members = reinterpret_cast<const int32_t*>(ds + o_mem);
+      b.cls_member_off = dev_ints(c, p.o.moff);
+      b.cls_members = dev_ints(c, p.o.mem);
     }
-    if (b.nstat && !c->inline_stats && !pair) {  // staged fill: ExclusionStats by fill_exclusion_kernel on stream3
-      HIPCHK(c, c->d_fill_lim.ensure(size_t(nruns) * size_t(s.N)));
+    if (b.nstat && !c->inline_stats && !f.pair) {  // staged fill: ExclusionStats by fill_exclusion_kernel on stream3
+      HIPCHK(c, c->d_fill_lim.ensure(size_t(p.nruns) * size_t(s.N)));
       b.stats_split = 1;
       b.fill_lim = c->d_fill_lim.p;
     }
     // partial slots per fill position: the exclusion grid (split), else the widest fill grid
-    b.nstat_blocks = int32_t(b.stats_split ? grid.x : pair ? pgx : nblk_fill);
-    b.rack_fanout = ragged_pair ? -1 : ucols <= 8 ? c->rack_fanout : 0;  // the fill fuses the first roll-up level
+    b.nstat_blocks = int32_t(b.stats_split ? grid.x : f.pair ? f.pgx : f.nblk_fill);
+    b.rack_fanout = f.ragged_pair ? -1 : ucols <= 8 ? c->rack_fanout : 0;  // the fill fuses the first roll-up level
     if (b.rack_fanout) {
       c->fill_paths |= b.rack_fanout < 0 ? KUEUE_TAS_PATH_RAGGED_ROLLUP : KUEUE_TAS_PATH_UNIFORM_ROLLUP;
-      if (ragged_pair) c->fill_paths |= KUEUE_TAS_PATH_RAGGED_PAIR;
+      if (f.ragged_pair) c->fill_paths |= KUEUE_TAS_PATH_RAGGED_PAIR;
       // positive-children masks are 64-bit: none when a ragged parent is wider
-      if (!ragged_pair || s.ragged_max_fan <= kWave) {
+      if (!f.ragged_pair || s.ragged_max_fan <= kWave) {
         HIPCHK(c, c->d_rack_pos.ensure(size_t(nfill) * size_t(s.level_size[s.L - 2])));
         b.rack_pos = c->d_rack_pos.p;
       }
     }
-    const bool ts = b.num_profiles <= kStagedProfiles;
+    f.ts = b.num_profiles <= kStagedProfiles;
     // global lookups in the eval loop: a nodeSelector column beyond the
     // staged label columns, or required node affinity
-    bool gl = false;
-    for (size_t i = 0; i < n && !gl; i++) {
-      gl = (hev[i].flags & (KUEUE_TAS_F_AFFINITY | KUEUE_TAS_F_SELECTOR_EXT)) != 0;
-      for (int k = 0; k < hev[i].nsel; k++) gl = gl || hev[i].sel_col[k] >= kStagedLabels;
+    for (size_t i = 0; i < n && !f.gl; i++) {
+      f.gl = (hev[i].flags & (KUEUE_TAS_F_AFFINITY | KUEUE_TAS_F_SELECTOR_EXT)) != 0;
+      for (int k = 0; k < hev[i].nsel; k++) f.gl = f.gl || hev[i].sel_col[k] >= kStagedLabels;
     }
     // leaf parents wider than a slot: zeroed before the ragged pair fill adds
     // its pieces' sums (the fill bracket and stream2's chunks start after it)
-    const bool wide = ragged_pair && s.n_wide > 0;
-    if (wide) {
+    f.wide = f.ragged_pair && s.n_wide > 0;
+    if (f.wide) {
       hipLaunchKernelGGL(wide_parents_zero_kernel, dim3(unsigned((s.n_wide + 255) / 256), unsigned(nfill)), dim3(256), 0,
                          c->stream, s, b);
       HIPCHK(c, hipGetLastError());
@@ -2965,118 +3245,46 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     // leaf categories in the single-run pair fill: every filter on staged
     // data (no affinity, no far selector column: !gl), taint rows and the
     // ExclusionStats in LDS, label ids packed in 16 bits
-    const bool cat = c->cat_fill && pair && !gl && ts && b.nstat > 0 && c->labels16;
+    f.cat = c->cat_fill && f.pair && !f.gl && f.ts && b.nstat > 0 && c->labels16;
     // the fast-LFC chunk tables accumulated by the fill itself (every chunk
     // runs on fill_pair_kernel: its lean loop from the block's (category,
     // value) pairs, its per-leaf loop per wave): no lfc_hist_kernel
     // re-reading the slot classes' leaf rows
-    b.lfc_fill = (nfast > 0 && pair && c->lfc_in_fill) ? 1 : 0;
+    b.lfc_fill = (p.nfast > 0 && f.pair && c->knobs.lfc_in_fill) ? 1 : 0;
     if (b.lfc_fill) c->fill_paths |= KUEUE_TAS_PATH_LFC_FILL;
-    if (b.lfc_fill && c->lfc_dirty[lfc_cur]) {  // (after a reallocation: zeroed before the fill)
+    if (b.lfc_fill && c->lfc_dirty[p.lfc_cur]) {  // (after a reallocation: zeroed before the fill)
       HIPCHK(c, hipMemsetAsync(b.lfc_ch, 0, c->lfc_half * kLfcBins * 4, c->stream));
       HIPCHK(c, hipMemsetAsync(b.lfc_ovs, 0, c->lfc_half * 8, c->stream));
-      c->lfc_dirty[lfc_cur] = false;
+      c->lfc_dirty[p.lfc_cur] = false;
     }
-    // single-run chunks [0, nsingle) and multi-run chunks [nsingle, nfchunks): one launch each
-    auto staged = [&](auto ns, auto tsv, auto mr, int first, int count, hipStream_t st) {
-      if (count <= 0) return;
-      constexpr int NSv = decltype(ns)::value;
-      constexpr bool TSv = decltype(tsv)::value, MRv = decltype(mr)::value;
-      if (pair) {  // kPairLP leaves per thread
-        c->fill_paths |= KUEUE_TAS_PATH_PAIR;
-        const dim3 pg(pgx, unsigned(count));
-        if constexpr (TSv && !MRv) {  // single-run chunks: leaf categories
-          if (cat) {
-            c->fill_paths |= KUEUE_TAS_PATH_CATEGORY;
-            if (b.lfc_fill) {  // (the lean loop's LFC pair lists in LDS)
-              if (ragged_pair)
-                hipLaunchKernelGGL((fill_pair_kernel<NSv, true, false, false, -1, true, true>), pg, dim3(256), 0, st, s, b, umask, first);
-              else if (b.rack_fanout == 32)
-                hipLaunchKernelGGL((fill_pair_kernel<NSv, true, false, false, 32, true, true>), pg, dim3(256), 0, st, s, b, umask, first);
-              else
-                hipLaunchKernelGGL((fill_pair_kernel<NSv, true, false, false, 0, true, true>), pg, dim3(256), 0, st, s, b, umask, first);
-            } else if (ragged_pair) {
-              hipLaunchKernelGGL((fill_pair_kernel<NSv, true, false, false, -1, true>), pg, dim3(256), 0, st, s, b, umask, first);
-            } else if (b.rack_fanout == 32) {
-              hipLaunchKernelGGL((fill_pair_kernel<NSv, true, false, false, 32, true>), pg, dim3(256), 0, st, s, b, umask, first);
-            } else {
-              hipLaunchKernelGGL((fill_pair_kernel<NSv, true, false, false, 0, true>), pg, dim3(256), 0, st, s, b, umask, first);
-            }
-            return;
-          }
-        }
-        if (ragged_pair && gl)
-          hipLaunchKernelGGL((fill_pair_kernel<NSv, TSv, MRv, true, -1>), pg, dim3(256), 0, st, s, b, umask, first);
-        else if (ragged_pair)
-          hipLaunchKernelGGL((fill_pair_kernel<NSv, TSv, MRv, false, -1>), pg, dim3(256), 0, st, s, b, umask, first);
-        else if (gl && b.rack_fanout == 32)
-          hipLaunchKernelGGL((fill_pair_kernel<NSv, TSv, MRv, true, 32>), pg, dim3(256), 0, st, s, b, umask, first);
-        else if (gl)
-          hipLaunchKernelGGL((fill_pair_kernel<NSv, TSv, MRv, true, 0>), pg, dim3(256), 0, st, s, b, umask, first);
-        else if (b.rack_fanout == 32)
-          hipLaunchKernelGGL((fill_pair_kernel<NSv, TSv, MRv, false, 32>), pg, dim3(256), 0, st, s, b, umask, first);
-        else
-          hipLaunchKernelGGL((fill_pair_kernel<NSv, TSv, MRv, false, 0>), pg, dim3(256), 0, st, s, b, umask, first);
-        return;
-      }
-      if (gl)
-        hipLaunchKernelGGL((fill_leaves_staged_kernel<NSv, TSv, MRv, true>), dim3(sgx, unsigned(count)), dim3(256), 0,
-                           st, s, b, umask, first);
-      else
-        hipLaunchKernelGGL((fill_leaves_staged_kernel<NSv, TSv, MRv, false>), dim3(sgx, unsigned(count)), dim3(256), 0,
-                           st, s, b, umask, first);
-    };
-    // the multi-run chunks (a few small signatures) run beside the single-run
-    // chunks on stream2 (idle until the fill is done): their launch's ramp and
-    // tail overlap the big launch instead of following it
-    auto staged2 = [&](auto ns, auto tsv) -> int {
-      const bool side = nsingle > 0 && nfchunks > nsingle;
-      if (side) {
-        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[1], 0));
-        staged(ns, tsv, std::true_type(), nsingle, nfchunks - nsingle, c->stream2);
-        HIPCHK(c, hipEventRecord(c->evl[2], c->stream2));
-      } else {
-        staged(ns, tsv, std::true_type(), nsingle, nfchunks - nsingle, c->stream);
-      }
-      staged(ns, tsv, std::false_type(), 0, nsingle, c->stream);
-      if (side) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evl[2], 0));
-      return 0;
-    };
-    using I4 = std::integral_constant<int, 4>;
-    using I5 = std::integral_constant<int, 5>;
-    using I8 = std::integral_constant<int, 8>;
-    int src = 0;
-    c->fill_paths |= ucols <= 8 ? (ts ? KUEUE_TAS_PATH_STAGED : KUEUE_TAS_PATH_STAGED_GLOBAL_TAINTS)
+    const int maxt = p.maxt;
+    c->fill_paths |= ucols <= 8 ? (f.ts ? KUEUE_TAS_PATH_STAGED : KUEUE_TAS_PATH_STAGED_GLOBAL_TAINTS)
                                 : maxt <= 4 ? KUEUE_TAS_PATH_GENERIC4 : maxt <= 8 ? KUEUE_TAS_PATH_GENERIC8
                                 : maxt <= 16 ? KUEUE_TAS_PATH_GENERIC16 : KUEUE_TAS_PATH_GENERIC32;
-    if (ucols <= 8 && gl) c->fill_paths |= KUEUE_TAS_PATH_STAGED_GL;
-    if (!lds_stats) c->fill_paths |= KUEUE_TAS_PATH_GLOBAL_STATS;
+    if (ucols <= 8 && f.gl) c->fill_paths |= KUEUE_TAS_PATH_STAGED_GL;
+    if (!p.lds_stats) c->fill_paths |= KUEUE_TAS_PATH_GLOBAL_STATS;
     if (b.stats_split) c->fill_paths |= b.num_profiles <= kStagedProfiles ? KUEUE_TAS_PATH_EXCL : KUEUE_TAS_PATH_EXCL_GLOBAL_TAINTS;
     for (size_t i = 0; i < n; i++)
       if (hev[i].sx_begin >= 0) c->fill_paths |= KUEUE_TAS_PATH_SELECTOR_EXT;
-    if (ucols <= 4 && ts) src = staged2(I4(), std::true_type());
-    else if (ucols <= 4) src = staged2(I4(), std::false_type());
-    else if (ucols <= 5 && ts) src = staged2(I5(), std::true_type());
-    else if (ucols <= 5) src = staged2(I5(), std::false_type());
-    else if (ucols <= 8 && ts) src = staged2(I8(), std::true_type());
-    else if (ucols <= 8) src = staged2(I8(), std::false_type());
-    else if (maxt <= 4) hipLaunchKernelGGL(fill_leaves_kernel<4>, grid, dim3(256), 0, c->stream, s, b);
-    else if (maxt <= 8) hipLaunchKernelGGL(fill_leaves_kernel<8>, grid, dim3(256), 0, c->stream, s, b);
-    else if (maxt <= 16) hipLaunchKernelGGL(fill_leaves_kernel<16>, grid, dim3(256), 0, c->stream, s, b);
-    else hipLaunchKernelGGL(fill_leaves_kernel<32>, grid, dim3(256), 0, c->stream, s, b);
-    if (src) return src;
+    if (const int rc = launch_fill(c, p, f, b, grid)) return rc;
     HIPCHK(c, hipGetLastError());
-    if (wide) {
+    if (f.wide) {
       hipLaunchKernelGGL(wide_parents_finish_kernel, dim3(unsigned((s.n_wide + 255) / 256), unsigned(nfill)), dim3(256),
                          0, c->stream, s, b);
       HIPCHK(c, hipGetLastError());
     }
   }
-  trace(13);
+  return KUEUE_TAS_OK;
+}
+
+// Stage 12a: the fill's end (ev[2], what stream2 and stream3 wait for) and the
+// ExclusionStats on stream3 beside the roll-up / select, joined before the
+// D2H: the reduce of the fill's per-block partials (counted inside the fill),
+// or the split path's counting kernel + reduce.
+static int enqueue_stats_branch(kueue_tas_ctx* c, const ChunkPlan& p, const DevBatch& b) {
+  const DevSnap& s = c->snap;
+  const int nfill = p.nfill, nfchunks = p.nfchunks;
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  // ExclusionStats on stream3 beside the roll-up / select, joined before the
-  // D2H: the reduce of the fill's per-block partials (counted inside the
-  // fill), or the split path's counting kernel + reduce
   const bool stats_branch = b.nstat > 0;
   if (stats_branch && !b.stats_split) {
     HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev[2], 0));
@@ -3096,7 +3304,16 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->evs[1], c->stream3));
   }
-  // K2
+  return KUEUE_TAS_OK;
+}
+
+// Stage 12b (K2): the roll-up of the levels the fill did not fuse, and the
+// level maxima for the BestFit-side find_level.
+static int enqueue_rollup(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p, DevBatch& b) {
+  const DevSnap& s = c->snap;
+  const size_t n = a.n;
+  const int nfill = p.nfill, nbf = p.nbf;
+  uint8_t* ds = c->d_stage.p;
   const int upper = s.L - 2 - (b.rack_fanout ? 1 : 0);  // levels [0, upper] left to roll up
   int top_parents = 0;  // parents above level `upper`: the fused launch's last block rolls them up
   for (int l = 0; l < upper; l++) top_parents += s.level_size[l];
@@ -3104,11 +3321,11 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
                          s.level_size[upper + 1] / s.level_size[upper] >= 8;
   if (fused_top) {  // every upper level and the level maxima in one launch
     c->fill_paths |= KUEUE_TAS_PATH_FUSED_TOP;
-    b.level_max = nbf > 0 ? reinterpret_cast<int32_t*>(ds + o_top) : nullptr;
+    b.level_max = nbf > 0 ? reinterpret_cast<int32_t*>(ds + p.o.top) : nullptr;
     const int per_block = 4 * kParentsPerWave;
     dim3 grid((s.level_size[upper] + per_block - 1) / per_block, unsigned(nfill));
     hipLaunchKernelGGL(rollup_top_kernel, grid, dim3(256), 0, c->stream, s, b, upper,
-                       reinterpret_cast<int32_t*>(ds + o_top) + n * kMaxLevels);
+                       reinterpret_cast<int32_t*>(ds + p.o.top) + n * kMaxLevels);
     HIPCHK(c, hipGetLastError());
   }
   // the small top levels (<= kTailParents domains) go to rollup_tail_kernel with the level maxima
@@ -3139,36 +3356,49 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     hipLaunchKernelGGL(rollup_tail_kernel, dim3(unsigned(nfill)), dim3(256), 0, c->stream, s, b, tail_top);
     HIPCHK(c, hipGetLastError());
   }
-  trace(14);
+  return KUEUE_TAS_OK;
+}
+
+// the class rep's exclusion stats go to the other members by replicate_kernel (global-atomic stats only)
+static bool stats_replicated(const ChunkPlan& p, const DevBatch& b) { return p.npairs && !b.nstat; }
+// KTAS_EMIT_MAIN: lfc_emit on the main stream after the BestFit select
+static bool emit_on_main(const kueue_tas_ctx* c, const ChunkPlan& p) {
+  return c->knobs.emit_after_bf && p.nbf > 0 && p.nfast > 0;
+}
+// select_kernel's per-wave LDS: the sort capacity (list_cap keys); the BestFit
+// side also holds lds_level_walk's candidates (kFinalWalkLds per wave)
+static int lfc_wave_lds(const kueue_tas_ctx* c) { return c->list_cap * 16; }
+static int bf_wave_lds(const kueue_tas_ctx* c) { return std::max(lfc_wave_lds(c), kFinalWalkLds); }
+
+// Stage 12c (K3): the stats replication, the leaf-level selection partials and
+// the BestFit-side select (every non-fast eval) on the main stream, one launch
+// per slot group.
+static int enqueue_bestfit_select(kueue_tas_ctx* c, const ChunkPlan& p, DevBatch& b) {
+  const DevSnap& s = c->snap;
+  const int npairs = p.npairs, nleafsel = p.nleafsel, nbf = p.nbf;
   if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-  const bool replicated = npairs && !b.nstat;
-  if (replicated) {  // exclusion stats of the class rep to the other members (global-atomic stats)
-    hipLaunchKernelGGL(replicate_kernel, dim3(1, unsigned(npairs)), dim3(256), 0, c->stream, s, b, d_pairs, npairs);
+  const bool replicated = stats_replicated(p, b);
+  if (replicated) {
+    hipLaunchKernelGGL(replicate_kernel, dim3(1, unsigned(npairs)), dim3(256), 0, c->stream, s, b, dev_ints(c, p.o.pairs),
+                       npairs);
     HIPCHK(c, hipGetLastError());
   }
   // an event on the main stream costs ~8 us of its device time (rocprof
   // kernel trace): recorded only when the fast-LFC branch waits for the
   // replication, or for the stage profile
   if (replicated || c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-  const int32_t* d_fast = reinterpret_cast<const int32_t*>(ds + o_fast);
-  const int32_t* d_bf = reinterpret_cast<const int32_t*>(ds + o_bf);
+  const int32_t* d_bf = dev_ints(c, p.o.bf);
   const int waves = kSelectWaves;  // the kernel's per-wave LDS state is sized for this
-  // per-wave LDS: the sort capacity (list_cap keys); the BestFit side also
-  // holds lds_level_walk's candidates (kFinalWalkLds per wave)
-  const int lfc_wave_lds = c->list_cap * 16, bf_wave_lds = std::max(lfc_wave_lds, kFinalWalkLds);
   // leaf-level selection partials (non-fast evals whose requested level is the leaf level)
   if (nleafsel && s.N > 0) {
     c->last_stats[1] += nleafsel;
     dim3 grid((s.N + 255) / 256, unsigned((nleafsel + kEvalsPerFillBlock - 1) / kEvalsPerFillBlock));
-    hipLaunchKernelGGL(leaf_partials_kernel, grid, dim3(256), 0, c->stream, s, b, d_leafsel, nleafsel);
+    hipLaunchKernelGGL(leaf_partials_kernel, grid, dim3(256), 0, c->stream, s, b, dev_ints(c, p.o.leafsel), nleafsel);
     HIPCHK(c, hipGetLastError());
   }
   if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-  const bool emit_main = c->emit_after_bf && nbf > 0 && nfast > 0;
-  const int emit_grid = int(std::min<int64_t>(int64_t(nfast) * nchunks, 2048));
-  // K3 (BestFit side and every other non-fast eval)
   if (nbf) {
-    b.wave_lds = bf_wave_lds;
+    b.wave_lds = bf_wave_lds(c);
     const int32_t epoch0 = c->tag_epoch;
     for (size_t gi = 0; gi + 1 < c->sel_groups.size(); gi++) {  // one launch per slot group (one, within budget)
       const int g0 = c->sel_groups[gi], gn = c->sel_groups[gi + 1] - g0;
@@ -3176,17 +3406,27 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
       b.tag_epoch = epoch0 + int32_t(gi);
       c->tag_epoch = b.tag_epoch;
       hipLaunchKernelGGL(select_kernel, dim3(unsigned((gn + waves - 1) / waves)), dim3(64 * waves),
-                         size_t(waves) * size_t(bf_wave_lds), c->stream, s, b, d_bf + g0, gn);
+                         size_t(waves) * size_t(b.wave_lds), c->stream, s, b, d_bf + g0, gn);
       HIPCHK(c, hipGetLastError());
     }
     b.slot_base = 0;
   }
-  trace(16);
+  return KUEUE_TAS_OK;
+}
+
+// Stage 12d: the fast-LFC branch on stream2: leaf tables (after the fill),
+// select + emit (after the stats replication); the main stream runs the
+// BestFit side.  Enqueued after the BestFit select: that launch is on the
+// batch's longest chain, and the host's calls for this branch would otherwise
+// delay it.
+static int enqueue_fast_lfc(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p, DevBatch& b) {
+  const DevSnap& s = c->snap;
+  const size_t n = a.n;
+  const int nfast = p.nfast, nslots = p.nslots, nchunks = p.nchunks, lfc_cur = p.lfc_cur;
+  const int waves = kSelectWaves;
+  const bool emit_main = emit_on_main(c, p);
+  const int emit_grid = int(std::min<int64_t>(int64_t(nfast) * nchunks, 2048));
   if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-  // fast-LFC branch on stream2: leaf tables (after the fill), select + emit
-  // (after the stats replication); the main stream runs the BestFit side.
-  // Enqueued after the BestFit select: that launch is on the batch's longest
-  // chain, and the host's calls for this branch would otherwise delay it
   if (nfast) {
     if (c->lfc_dirty[lfc_cur ^ 1]) {  // the next batch's half, zeroed while this batch runs
       HIPCHK(c, hipMemsetAsync(c->d_lfc_ch.p + size_t(lfc_cur ^ 1) * c->lfc_half * kLfcBins, 0,
@@ -3206,12 +3446,12 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     HIPCHK(c, hipGetLastError());
     // the fast-LFC select reads the leaf counters and the LFC tables only
     // (lfc_fast): it waits for the roll-up only when the replication wrote stats
-    if (replicated) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[4], 0));
-    b.wave_lds = lfc_wave_lds;
+    if (stats_replicated(p, b)) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[4], 0));
+    b.wave_lds = lfc_wave_lds(c);
     const SelSlot* sel = b.sel_slots;
     b.sel_slots = nullptr;  // fast-LFC evals keep no lists or overlay
     hipLaunchKernelGGL(select_kernel, dim3(unsigned((nfast + waves - 1) / waves)), dim3(64 * waves),
-                       size_t(waves) * size_t(lfc_wave_lds), c->stream2, s, b, d_fast, nfast);
+                       size_t(waves) * size_t(b.wave_lds), c->stream2, s, b, dev_ints(c, p.o.fast), nfast);
     b.sel_slots = sel;
     HIPCHK(c, hipGetLastError());
     if (emit_main) {
@@ -3224,7 +3464,7 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     // the branch's result headers come back on its own stream: the host
     // waits for both streams instead of the main stream waiting for this one
     // (a cross-stream hand-off costs ~17 us of device time, sync_cost.hip)
-    HIPCHK(c, hipMemcpyAsync(c->h_res2.p, d_out, n * sizeof(kueue_tas_eval_out), hipMemcpyDeviceToHost, c->stream2));
+    HIPCHK(c, hipMemcpyAsync(c->h_res2.p, c->d_res.p, n * sizeof(kueue_tas_eval_out), hipMemcpyDeviceToHost, c->stream2));
   }
   if (nfast && emit_main) {  // the emit after the BestFit select on the main stream (its chunk re-reads
     // stall the descents beside it); the fast select's items from stream2
@@ -3232,65 +3472,94 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     hipLaunchKernelGGL(lfc_emit_kernel, dim3(unsigned(emit_grid)), dim3(256), 0, c->stream, s, b);
     HIPCHK(c, hipGetLastError());
   }
-  trace(15);
-  if (stats_branch) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evs[1], 0));  // join the ExclusionStats branch
+  return KUEUE_TAS_OK;
+}
+
+// the join of the ExclusionStats branch and the results' D2H on the main stream
+static int enqueue_results_d2h(kueue_tas_ctx* c, const ChunkPlan& p, const DevBatch& b) {
+  if (b.nstat > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evs[1], 0));
   if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_res.p, c->d_res.p, res_bytes, hipMemcpyDeviceToHost, c->stream));
-  lap(2);
-  trace(17);
-  // the speculative class merge verified exactly while the device runs
+  HIPCHK(c, hipMemcpyAsync(c->h_res.p, c->d_res.p, p.res_bytes, hipMemcpyDeviceToHost, c->stream));
+  return KUEUE_TAS_OK;
+}
+
+// Stage 13: the speculative class merge (merge_classes) verified exactly while
+// the device runs; false: a 64-bit class hash collision.
+static bool verify_merge(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p) {
+  if (c->exact_merge) return true;
+  const DevEval* hev = stage_evals(c, p);
+  const ClassKeys keys(c, a, p);
+  const std::vector<int32_t>& cls_rep = c->cls_rep;
   bool merge_ok = true;
-  if (!c->exact_merge) {
-    const std::vector<int32_t>& cls_rep = c->cls_rep;
-    for (size_t t = 0; t < nparts && merge_ok; t++) {
-      const PartClasses& pc = c->part_cls[t];
-      for (size_t j = 0; j < pc.rep.size() && merge_ok; j++) {
-        const int32_t r = cls_rep[size_t(c->part_map[c->part_base[t] + j])];
-        if (r != pc.rep[j]) merge_ok = same_sig(hev[pc.rep[j]], hev[r]) && same_mask(hev[pc.rep[j]], hev[r]);
-      }
-    }
-    for (size_t k = 0; k < cls_rep.size() && merge_ok; k++) {
-      const int32_t g = c->sig_rep[size_t(c->cls_sig[k])];
-      if (g != cls_rep[k]) merge_ok = same_sig(hev[cls_rep[k]], hev[g]);
+  for (size_t t = 0; t < c->part_cls.size() && merge_ok; t++) {
+    const PartClasses& pc = c->part_cls[t];
+    for (size_t j = 0; j < pc.rep.size() && merge_ok; j++) {
+      const int32_t r = cls_rep[size_t(c->part_map[c->part_base[t] + j])];
+      if (r != pc.rep[j]) merge_ok = keys.same_sig(hev[pc.rep[j]], hev[r]) && keys.same_mask(hev[pc.rep[j]], hev[r]);
     }
   }
+  for (size_t k = 0; k < cls_rep.size() && merge_ok; k++) {
+    const int32_t g = c->sig_rep[size_t(c->cls_sig[k])];
+    if (g != cls_rep[k]) merge_ok = keys.same_sig(hev[cls_rep[k]], hev[g]);
+  }
+  return merge_ok;
+}
+
+// Stage 14: the batch's one sync (both streams with fast-LFC evals, whose
+// result headers come back on stream2), then the two conditions that re-run
+// the chunk as it is; claim_entry_regions holds the third, which grows entry_cap.
+static int sync_and_check(kueue_tas_ctx* c, const ChunkPlan& p, bool merge_ok) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (nfast) {
+  if (p.nfast) {
     HIPCHK(c, hipStreamSynchronize(c->stream2));
-    const int32_t* hf = reinterpret_cast<const int32_t*>(hs + o_fast);
-    for (int k = 0; k < nfast; k++) c->res_out_h[hf[k]] = c->h_res2.p[hf[k]];
+    const int32_t* hf = stage_ints(c, p.o.fast);
+    for (int k = 0; k < p.nfast; k++) c->res_out_h[hf[k]] = c->h_res2.p[hf[k]];
   }
   if (!merge_ok) {  // a 64-bit class hash collision: the caller re-runs the chunk with the exact merge
     c->exact_merge = true;
     c->merge_reruns++;
-    return 2;
+    return ChunkRerun;
   }
-  if (!c->scratch_full && c->scratch_bounded) {  // a bounded list overflowed: re-run with unbounded lists
-    const int32_t* hb = reinterpret_cast<const int32_t*>(hs + o_bf);
-    const SelSlot* hq = reinterpret_cast<const SelSlot*>(hs + o_sel);
-    for (int k = 0; k < nbf; k++) {
+  if (!c->scratch_full && c->knobs.scratch_bounded) {  // a bounded list overflowed: re-run with unbounded lists
+    const int32_t* hb = stage_ints(c, p.o.bf);
+    const SelSlot* hq = reinterpret_cast<const SelSlot*>(c->h_stage.p + p.o.sel);
+    for (int k = 0; k < p.nbf; k++) {
       const kueue_tas_eval_out& o = c->res_out_h[hb[k]];
-      if ((o.status == KUEUE_TAS_ST_INTERNAL && o.num_workers + o.num_leaders <= entry_cap && hq[k].lcap < full_lcap) ||
-          c->force_scratch_rerun) {
+      if ((o.status == KUEUE_TAS_ST_INTERNAL && o.num_workers + o.num_leaders <= c->entry_cap && hq[k].lcap < p.full_lcap) ||
+          c->knobs.force_scratch_rerun) {
         c->scratch_full = true;
         c->scratch_reruns++;
-        return 2;
+        return ChunkRerun;
       }
     }
   }
-  lap(3);
-  trace(18);
+  return KUEUE_TAS_OK;
+}
+
+// The chunk's entry regions claimed (see ensure_entry_regions for the sizes):
+// the strided offsets, each eval's pair count, ent_used.  An assignment longer
+// than entry_cap: nothing claimed, the caller grows entry_cap and re-runs.
+static int claim_entry_regions(kueue_tas_ctx* c, const ChunkArgs& a) {
+  const size_t n = a.n;
+  const int32_t entry_cap = c->entry_cap;
   int32_t need = 0;
   for (size_t i = 0; i < n; i++) need = std::max(need, c->res_out_h[i].num_workers + c->res_out_h[i].num_leaders);
-  if (need > entry_cap) return 1;  // caller grows entry_cap and re-runs this chunk
+  if (need > entry_cap) return ChunkGrowEntries;
   const int64_t base_pairs = int64_t(c->ent_used / 2);
-  for (size_t i = 0; i <= n; i++) offsets[i] = base_pairs + int64_t(i) * entry_cap;  // strided regions
+  for (size_t i = 0; i <= n; i++) a.offsets[i] = base_pairs + int64_t(i) * entry_cap;  // strided regions
   for (size_t i = 0; i < n; i++)
     c->ent_count.push_back(std::min(c->res_out_h[i].num_workers + c->res_out_h[i].num_leaders, entry_cap));
-  c->ent_used += size_t(n) * size_t(entry_cap) * 2;
+  c->ent_used += n * size_t(entry_cap) * 2;
   c->ent_stride = entry_cap;
-  lap(4);
-  trace(19);
+  return KUEUE_TAS_OK;
+}
+
+// Stage 15a: results and ExclusionStats to the caller's arrays
+static int copy_out(kueue_tas_ctx* c, const ChunkArgs& a) {
+  const DevSnap& s = c->snap;
+  const size_t n = a.n;
+  const size_t nt = size_t(std::max(a.num_taints, 0));
+  kueue_tas_eval_out* out = a.out;
   memcpy(out, c->res_out_h, n * sizeof(kueue_tas_eval_out));
   {  // nodeSelector / affinity exclusions: counted beside select (stream3), read from the stats region after the join
     const int32_t* sel = c->res_stats_h + n * nt + n * size_t(s.R);
@@ -3311,15 +3580,22 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
     c->last_ticks.push_back(c->res_out_h[i].reserved[0]);
     c->last_ticks.push_back(c->res_out_h[i].reserved[1]);
   }
-  if (taint_counts && nt) memcpy(taint_counts, c->res_stats_h, n * nt * 4);
-  if (res_counts && s.R) memcpy(res_counts, c->res_stats_h + n * nt, n * size_t(s.R) * 4);
+  if (a.taint_counts && nt) memcpy(a.taint_counts, c->res_stats_h, n * nt * 4);
+  if (a.res_counts && s.R) memcpy(a.res_counts, c->res_stats_h + n * nt, n * size_t(s.R) * 4);
+  return KUEUE_TAS_OK;
+}
+
+// Stage 15b: the device stage times from the chunk's events, added to the batch's
+static void collect_stage_times(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p, const DevBatch& b) {
+  float* ms = a.ms;
+  float* stage_ms = a.stage_ms;
+  const int nfast = p.nfast;
   float st[KUEUE_TAS_NUM_STAGES] = {};
   if (!c->stage_timing) {  // only the fill bracket (ev1 -> ev2) was recorded
     (void)hipEventElapsedTime(&st[0], c->ev[1], c->ev[2]);
     for (int k = 0; k < KUEUE_TAS_NUM_STAGES; k++) stage_ms[k] += st[k];
     ms[0] += st[0];
-    lap(5);
-    return KUEUE_TAS_OK;
+    return;
   }
   for (int k = 0; k < 6; k++) (void)hipEventElapsedTime(&st[k], c->ev[k + 1], c->ev[k + 2]);
   const float partials = st[3];  // ev4 -> ev5: leaf partials; stage [3] reports the concurrent fast-LFC branch
@@ -3337,6 +3613,65 @@ static int eval_chunk(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, s
   ms[1] += st[1] + st[2];            // roll-up + replication
   ms[2] += partials + st[4] + st[5]; // leaf partials + select + join with the fast-LFC branch
   ms[3] += st[6];
+}
+
+static int eval_chunk(kueue_tas_ctx* c, const ChunkArgs& a) {
+  ChunkPlan p;
+  DevBatch b{};
+  int rc;
+  double tm = wall_ms();
+  auto lap = [&](int k) {
+    const double t = wall_ms();
+    c->host_ms[k] += t - tm;
+    tm = t;
+  };
+  trace(c, 0);
+  if ((rc = validate_requests(c, a))) return rc;
+  c->host_ms[6] += wall_ms() - tm;
+  trace(c, 1);
+  if ((rc = layout_stage(c, a, p))) return rc;
+  trace(c, 2);
+  const double t_b = wall_ms();
+  if ((rc = compile_requests(c, a, p))) return rc;
+  c->host_ms[7] += wall_ms() - t_b;
+  trace(c, 3);
+  copy_tables(c, a, p);
+  lap(0);
+  trace(c, 4);
+  merge_classes(c, a, p);
+  trace(c, 5);
+  assign_reps_and_slots(c, a, p);
+  trace(c, 6);
+  order_fill_chunks(c, a, p);  // (trace points 7, 8)
+  lap(1);
+  trace(c, 9);
+  if ((rc = size_device_buffers(c, a, p))) return rc;
+  if ((rc = ensure_entry_regions(c, a))) return rc;
+  trace(c, 10);
+  build_fill_records(c, a, p);
+  trace(c, 11);
+  if ((rc = upload_and_describe(c, a, p, b))) return rc;  // (trace point 12)
+  if ((rc = enqueue_fill(c, a, p, b))) return rc;
+  trace(c, 13);
+  if ((rc = enqueue_stats_branch(c, p, b))) return rc;
+  if ((rc = enqueue_rollup(c, a, p, b))) return rc;
+  trace(c, 14);
+  if ((rc = enqueue_bestfit_select(c, p, b))) return rc;
+  trace(c, 16);
+  if ((rc = enqueue_fast_lfc(c, a, p, b))) return rc;
+  trace(c, 15);
+  if ((rc = enqueue_results_d2h(c, p, b))) return rc;
+  lap(2);
+  trace(c, 17);
+  const bool merge_ok = verify_merge(c, a, p);
+  if ((rc = sync_and_check(c, p, merge_ok))) return rc;
+  lap(3);
+  trace(c, 18);
+  if ((rc = claim_entry_regions(c, a))) return rc;
+  lap(4);
+  trace(c, 19);
+  if ((rc = copy_out(c, a))) return rc;
+  collect_stage_times(c, a, p, b);
   lap(5);
   return KUEUE_TAS_OK;
 }
@@ -3364,8 +3699,6 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* c, const kueue_tas_eval_req* const*
                               const int32_t* affinity_values, size_t num_affinity_values, kueue_tas_eval_out* out,
                               int64_t* entry_offsets, int32_t* entries, size_t entries_capacity, int32_t* taint_counts,
                               int32_t* res_counts) {
-  // g_select_snap is one per device: batches of different contexts must not interleave
-  static std::mutex select_snap_mu;
   std::lock_guard<std::mutex> select_snap_lock(select_snap_mu);
   if (!c) return KUEUE_TAS_EINVAL;
   if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
@@ -3384,29 +3717,35 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* c, const kueue_tas_eval_req* const*
   const size_t chunk = size_t(c->max_batch);
   std::vector<int64_t> off;
   entry_offsets[0] = 0;
+  ChunkArgs a{reqs,     n,           taint_table,     taint_table_len,     num_taints, assumed, num_assumed,
+              affinity, num_affinity, affinity_values, num_affinity_values, out,        nullptr, taint_counts,
+              res_counts, ms,         stage_ms};
   for (size_t i0 = 0; i0 < n; i0 += chunk) {
     size_t m = std::min(chunk, n - i0);
     off.assign(m + 1, 0);
     c->chunk_base = i0;
+    a.reqs = reqs + i0;
+    a.n = m;
+    a.out = out + i0;
+    a.offsets = off.data();
+    a.taint_counts = taint_counts ? taint_counts + i0 * size_t(std::max(num_taints, 0)) : nullptr;
+    a.res_counts = res_counts ? res_counts + i0 * size_t(c->snap.R) : nullptr;
+    const size_t keep = c->ent_used;
+    auto rewind = [&] {  // what a chunk that re-runs recorded for the batch
+      c->ent_used = keep;
+      c->ent_count.resize(i0);
+      c->last_ticks.resize(2 * i0);
+      c->last_prof.resize(KTAS_PROFILE ? i0 * P_NCAT : 0);
+    };
     for (;;) {
-      size_t keep = c->ent_used;
-      int rc = eval_chunk(c, reqs + i0, m, taint_table, taint_table_len, num_taints, assumed, num_assumed, affinity,
-                          num_affinity, affinity_values, num_affinity_values, out + i0,
-                          off.data(), taint_counts ? taint_counts + i0 * size_t(std::max(num_taints, 0)) : nullptr,
-                          res_counts ? res_counts + i0 * size_t(c->snap.R) : nullptr, ms, stage_ms);
-      if (rc == 2) {  // a class hash collision (re-run with the exact merge) or a select list overflow (unbounded lists)
-        c->ent_used = keep;
-        c->ent_count.resize(i0);
-        c->last_ticks.resize(2 * i0);
-        c->last_prof.resize(KTAS_PROFILE ? i0 * P_NCAT : 0);
+      int rc = eval_chunk(c, a);
+      if (rc == ChunkRerun) {
+        rewind();
         continue;
       }
       c->exact_merge = false;
-      if (rc == 1) {  // an assignment exceeded the per-eval device capacity: grow and re-run
-        c->ent_used = keep;
-        c->ent_count.resize(i0);
-        c->last_ticks.resize(2 * i0);
-        c->last_prof.resize(KTAS_PROFILE ? i0 * P_NCAT : 0);
+      if (rc == ChunkGrowEntries) {
+        rewind();
         int32_t need = 0;
         for (size_t i = 0; i < m; i++) need = std::max(need, c->res_out_h[i].num_workers + c->res_out_h[i].num_leaders);
         int cap = c->entry_cap;
