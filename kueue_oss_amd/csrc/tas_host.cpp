@@ -2662,41 +2662,95 @@ struct AssumedUsage {
   }
 };
 
+using BatchList = std::vector<std::pair<size_t, GroupEval*>>;  // (workload, its group of the pass)
+
+// What one pass hands to kueue_tas_eval_batch_ptrs: request i is batch[i]'s
+// own record, referenced in place, and holds its offsets into the tables.
+struct PassTables {
+  std::vector<const kueue_tas_eval_req*> reqs;
+  std::vector<int32_t> taint;  // distinct taint rows
+  std::vector<kueue_tas_assumed> assumed;
+  std::vector<kueue_tas_affinity_req> aff;  // required affinity and nodeSelector pairs beyond the inline ones
+  std::vector<int32_t> aff_vals;
+  BatchList batch;
+  BatchList early;  // groups that failed host-side validation: reported, not evaluated
+  void clear() {    // keeps capacity
+    reqs.clear();
+    taint.clear();
+    assumed.clear();
+    aff.clear();
+    aff_vals.clear();
+    batch.clear();
+    early.clear();
+  }
+};
+
+// Appends g's affinity requirements, then its nodeSelector pairs beyond the
+// inline ones, to the tables (`begin` rebased from the group's own value
+// lists) and writes their ranges into q.
+static void append_affinity(const GroupEval& g, std::vector<kueue_tas_affinity_req>& aff, std::vector<int32_t>& vals,
+                            kueue_tas_eval_req& q) {
+  auto append = [&](const std::vector<kueue_tas_affinity_req>& recs, const std::vector<int32_t>& v) {
+    const int32_t vb = int32_t(vals.size());
+    for (auto r : recs) {
+      r.begin += vb;
+      aff.push_back(r);
+    }
+    vals.insert(vals.end(), v.begin(), v.end());
+  };
+  q.affinity_begin = int32_t(aff.size());
+  if (q.flags & KUEUE_TAS_F_AFFINITY) append(g.aff, g.aff_vals);
+  q.affinity_end = q.selector_begin = int32_t(aff.size());
+  if (q.flags & KUEUE_TAS_F_SELECTOR_EXT) append(g.sel_ext, g.sel_vals);
+  q.selector_end = int32_t(aff.size());
+}
+
+// One run's diagnostics.  The enumerators name the positions the
+// kueue_tas_host_last_* getters publish.
+struct RunDiag {
+  enum { kPrepare, kEvalCall /* incl. device */, kDecode, kTotal };           // host_ms
+  enum { kGrouping /* + column check */, kCompile, kBuildPass, kValues };    // detail_ms
+  enum { kBatches, kEvals, kLeaderEvals };                                    // counts
+  // stats: kueue_tas_last_stats in its order (summed; staged columns: max),
+  // then the OR of the fill paths and the alias fill rows
+  enum { kPhase1Evals, kPartialEvals, kFillLaunches, kStagedCols, kFillPaths, kAliasFills };
+  float ms[4] = {};                           // kueue_tas_last_timings, summed over the run's batches
+  float stage_ms[KUEUE_TAS_NUM_STAGES] = {};  // kueue_tas_last_stage_times, summed
+  double dev_host_ms[8] = {};                 // kueue_tas_last_host_times, summed
+  double host_ms[4] = {};
+  double detail_ms[4] = {};
+  int64_t counts[3] = {};
+  int64_t stats[6] = {};
+};
+
 struct Evaluator {
   FlavorSnapshot* snap;
-  float ms[4] = {0, 0, 0, 0};
-  float stage_ms[KUEUE_TAS_NUM_STAGES] = {};
-  double dev_host_ms[8] = {};
-  double host_ms[4] = {0, 0, 0, 0};  // prepare, eval call (incl. device), decode, total
-  double detail_ms[4] = {0, 0, 0, 0};  // grouping + column check, request compile, build_pass, Values
-  int64_t counts[3] = {0, 0, 0};
-  int64_t stats[6] = {0, 0, 0, 0, 0, 0};  // kueue_tas_last_stats summed over the run's batches, [4] fill paths,
-                                          // [5] alias fill rows
-  std::vector<const kueue_tas_eval_req*> reqs;  // the batch's requests: the groups' own records, by address
-  std::vector<int32_t> taint_table;
-  std::vector<kueue_tas_assumed> assumed;
-  std::vector<kueue_tas_affinity_req> aff;
-  std::vector<int32_t> affv;
+  RunDiag diag;
+  PassTables cur;  // the current pass
+  // first pass (every workload's first group, no assumed usage) cached for
+  // repeated runs over the same compiled workloads (run_compiled)
+  PassTables first;
+  const std::vector<Workload>* p0_for = nullptr;
+  uint64_t p0_gen = 0;
   std::vector<kueue_tas_eval_out> outs;
   std::vector<int64_t> offsets;
   std::vector<int32_t> entries, taint_counts, res_counts;
-  std::vector<std::pair<size_t, GroupEval*>> batch;
-  // first pass (every workload's first group, no assumed usage) cached for
-  // repeated runs over the same compiled workloads (run_compiled)
-  const std::vector<Workload>* p0_for = nullptr;
-  uint64_t p0_gen = 0;
-  std::vector<const kueue_tas_eval_req*> p0_reqs;
-  std::vector<int32_t> p0_taint;
-  std::vector<kueue_tas_affinity_req> p0_aff;
-  std::vector<int32_t> p0_affv;
-  std::vector<std::pair<size_t, GroupEval*>> p0_batch, p0_early;
-  std::vector<size_t> used;  // results set per workload in this run
-  std::string reasonBuf;
+  std::vector<size_t> used;  // results set per workload in this run (a member: its storage is reused)
   // the run's last device batch (request i belongs to workload (*ctr_bt)[i].first);
   // null when its counters are gone (kueue_tas_host_last_counters)
-  const std::vector<std::pair<size_t, GroupEval*>>* ctr_bt = nullptr;
+  const BatchList* ctr_bt = nullptr;
   kueue_tas_ctx* ctr_ctx = nullptr;  // the context and its kueue_tas_eval_generation right after that batch
   uint64_t ctr_gen = 0;
+  // what lives across a run's passes
+  struct RunState {
+    std::vector<Workload>& wls;
+    std::vector<std::vector<PodSetResult>>& results;
+    std::vector<char> done;
+    std::vector<AssumedUsage> assumedBy;
+    size_t pass = 0;
+    size_t T = 0, R = 0;  // taint strings, resource columns
+    double t_start = 0, t_prep = 0;  // start of the run, of the current pass's preparation
+  };
 
   // Results are updated in place (member order = first set in this run), so
   // repeated runs reuse the strings' and vectors' storage.
@@ -2720,64 +2774,40 @@ struct Evaluator {
   }
 
   // requests of one pass: taint rows shared through rowOff, assumed usage per workload
-  void build_pass(std::vector<Workload>& wls, size_t pass, const std::vector<char>& done,
-                  std::vector<AssumedUsage>& assumedBy,
-                  std::vector<const kueue_tas_eval_req*>& rq, std::vector<int32_t>& tt, std::vector<kueue_tas_assumed>& as,
-                  std::vector<kueue_tas_affinity_req>& af, std::vector<int32_t>& afv,
-                  std::vector<std::pair<size_t, GroupEval*>>& bt, std::vector<std::pair<size_t, GroupEval*>>& early) {
-    rq.clear();
-    tt.clear();
-    as.clear();
-    af.clear();
-    afv.clear();
-    bt.clear();
-    early.clear();
+  void build_pass(RunState& st, PassTables& t) {
+    t.clear();
+    // offset of a taint row in t.taint, appended when new
     std::map<std::vector<int32_t>, int32_t> rowOff;
     const std::vector<int32_t>* lastRow = nullptr;
     int32_t lastOff = 0;
-    for (size_t w = 0; w < wls.size(); w++) {
-      if (done[w] || pass >= wls[w].groups.size()) continue;
-      GroupEval& g = wls[w].groups[pass];
+    auto row_offset = [&](const std::vector<int32_t>& row) {
+      if (!lastRow || *lastRow != row) {  // consecutive requests mostly share a row
+        auto it = rowOff.find(row);
+        if (it == rowOff.end()) {
+          it = rowOff.emplace(row, int32_t(t.taint.size())).first;
+          t.taint.insert(t.taint.end(), row.begin(), row.end());
+        }
+        lastRow = &row;
+        lastOff = it->second;
+      }
+      return lastOff;
+    };
+    std::vector<kueue_tas_assumed>& as = t.assumed;
+    for (size_t w = 0; w < st.wls.size(); w++) {
+      if (st.done[w] || st.pass >= st.wls[w].groups.size()) continue;
+      GroupEval& g = st.wls[w].groups[st.pass];
       if (!g.early_reason.empty()) {
-        early.emplace_back(w, &g);
+        t.early.emplace_back(w, &g);
         continue;
       }
       // the batch tables' offsets go into the group's own record, which the
       // batch references in place (kueue_tas_eval_batch_ptrs: no copy)
       kueue_tas_eval_req& q = g.req;
-      rq.push_back(&q);
-      if (!lastRow || *lastRow != g.taint_row) {  // consecutive requests mostly share a row
-        auto it = rowOff.find(g.taint_row);
-        if (it == rowOff.end()) {
-          it = rowOff.emplace(g.taint_row, int32_t(tt.size())).first;
-          tt.insert(tt.end(), g.taint_row.begin(), g.taint_row.end());
-        }
-        lastRow = &g.taint_row;
-        lastOff = it->second;
-      }
-      q.taint_table = lastOff;
-      q.affinity_begin = int32_t(af.size());
-      if (q.flags & KUEUE_TAS_F_AFFINITY) {  // rebase the group's requirements into the batch tables
-        const int32_t vb = int32_t(afv.size());
-        for (auto r : g.aff) {
-          r.begin += vb;
-          af.push_back(r);
-        }
-        afv.insert(afv.end(), g.aff_vals.begin(), g.aff_vals.end());
-      }
-      q.affinity_end = int32_t(af.size());
-      q.selector_begin = q.selector_end = int32_t(af.size());
-      if (q.flags & KUEUE_TAS_F_SELECTOR_EXT) {  // nodeSelector pairs beyond the inline ones, same tables
-        const int32_t vb = int32_t(afv.size());
-        for (auto r : g.sel_ext) {
-          r.begin += vb;
-          af.push_back(r);
-        }
-        afv.insert(afv.end(), g.sel_vals.begin(), g.sel_vals.end());
-        q.selector_end = int32_t(af.size());
-      }
+      t.reqs.push_back(&q);
+      q.taint_table = row_offset(g.taint_row);
+      append_affinity(g, t.aff, t.aff_vals, q);
       q.assumed_begin = int32_t(as.size());
-      const std::vector<kueue_tas_assumed>& mine = assumedBy[w].records();
+      const std::vector<kueue_tas_assumed>& mine = st.assumedBy[w].records();
       if (base && !(*base)[w].empty()) {  // merge the base overlay with the group's assumed usage
         const Overlay& b = (*base)[w];
         size_t k = 0;
@@ -2793,7 +2823,7 @@ struct Evaluator {
         as.insert(as.end(), mine.begin(), mine.end());
       }
       q.assumed_end = int32_t(as.size());
-      bt.emplace_back(w, &g);
+      t.batch.emplace_back(w, &g);
     }
   }
 
@@ -2805,127 +2835,91 @@ struct Evaluator {
   // tables and rebases its records' offsets.  Same batch as build_pass
   // (taint rows are deduplicated within a part only: equal rows compare
   // equal by value wherever they are).
-  struct alignas(64) PartBatch {  // one per host part, on cache lines of its own
-    std::vector<const kueue_tas_eval_req*> rq;
-    std::vector<std::pair<size_t, GroupEval*>> bt, early;
-    std::vector<int32_t> tt;
+  struct alignas(64) PartBatch : PassTables {  // one per host part, on cache lines of its own; offsets part-local
     std::vector<std::pair<const std::vector<int32_t>*, int32_t>> rows;  // distinct rows of the part, local offsets
-    std::vector<kueue_tas_affinity_req> af;
-    std::vector<int32_t> afv;
-    size_t rqb = 0, ttb = 0, afb = 0, afvb = 0;
+    size_t rqb = 0, ttb = 0, afb = 0, afvb = 0;  // where the part's share starts in the batch tables
+    void clear() {
+      PassTables::clear();
+      rows.clear();
+    }
+    int32_t row_offset(const std::vector<int32_t>& row) {  // in taint, appended when new
+      for (auto& r : rows)  // a handful of distinct rows per batch
+        if (r.first == &row || *r.first == row) return r.second;
+      rows.emplace_back(&row, int32_t(taint.size()));
+      taint.insert(taint.end(), row.begin(), row.end());
+      return rows.back().second;
+    }
   };
   std::vector<PartBatch> partBatch;
-  void build_pass0_static(std::vector<Workload>& wls, const std::vector<char>& done,
-                          std::vector<const kueue_tas_eval_req*>& rq, std::vector<int32_t>& tt,
-                          std::vector<kueue_tas_assumed>& as, std::vector<kueue_tas_affinity_req>& af,
-                          std::vector<int32_t>& afv, std::vector<std::pair<size_t, GroupEval*>>& bt,
-                          std::vector<std::pair<size_t, GroupEval*>>& early) {
+  void build_pass0_static(RunState& st, PassTables& t) {
     HostPool& pool = HostPool::get();
-    const size_t T = pool.parts(), W = wls.size();
+    const size_t T = pool.parts(), W = st.wls.size();
     partBatch.resize(T);
     // every part is cleared here, not in its task: run_static skips empty
     // parts (W < parts()), and a part left from a larger batch would still
     // be merged below with pointers into that batch's workloads
-    for (auto& pb : partBatch) {
-      pb.rq.clear();
-      pb.bt.clear();
-      pb.early.clear();
-      pb.tt.clear();
-      pb.rows.clear();
-      pb.af.clear();
-      pb.afv.clear();
-    }
+    for (auto& pb : partBatch) pb.clear();
     auto part_of = [&](size_t b) {
-      size_t t = 0;
-      while (t + 1 < T && HostPool::part_begin(W, t + 1, T) <= b) t++;
-      return t;
+      size_t p = 0;
+      while (p + 1 < T && HostPool::part_begin(W, p + 1, T) <= b) p++;
+      return p;
     };
     pool.run_static(W, [&](size_t b, size_t e) {
       PartBatch& pb = partBatch[part_of(b)];
       for (size_t w = b; w < e; w++) {
-        if (done[w] || wls[w].groups.empty()) continue;
-        GroupEval& g = wls[w].groups[0];
+        if (st.done[w] || st.wls[w].groups.empty()) continue;
+        GroupEval& g = st.wls[w].groups[0];
         if (!g.early_reason.empty()) {
           pb.early.emplace_back(w, &g);
           continue;
         }
         kueue_tas_eval_req& q = g.req;
-        pb.rq.push_back(&q);
-        int32_t off = -1;
-        for (auto& r : pb.rows)  // a handful of distinct rows per batch
-          if (r.first == &g.taint_row || *r.first == g.taint_row) {
-            off = r.second;
-            break;
-          }
-        if (off < 0) {
-          off = int32_t(pb.tt.size());
-          pb.rows.emplace_back(&g.taint_row, off);
-          pb.tt.insert(pb.tt.end(), g.taint_row.begin(), g.taint_row.end());
-        }
-        q.taint_table = off;  // part-local offsets: rebased below
-        q.affinity_begin = int32_t(pb.af.size());
-        if (q.flags & KUEUE_TAS_F_AFFINITY) {
-          const int32_t vb = int32_t(pb.afv.size());
-          for (auto r : g.aff) {
-            r.begin += vb;
-            pb.af.push_back(r);
-          }
-          pb.afv.insert(pb.afv.end(), g.aff_vals.begin(), g.aff_vals.end());
-        }
-        q.affinity_end = int32_t(pb.af.size());
-        q.selector_begin = q.selector_end = int32_t(pb.af.size());
-        if (q.flags & KUEUE_TAS_F_SELECTOR_EXT) {
-          const int32_t vb = int32_t(pb.afv.size());
-          for (auto r : g.sel_ext) {
-            r.begin += vb;
-            pb.af.push_back(r);
-          }
-          pb.afv.insert(pb.afv.end(), g.sel_vals.begin(), g.sel_vals.end());
-          q.selector_end = int32_t(pb.af.size());
-        }
+        pb.reqs.push_back(&q);
+        q.taint_table = pb.row_offset(g.taint_row);  // part-local offsets: rebased below
+        append_affinity(g, pb.aff, pb.aff_vals, q);
         q.assumed_begin = q.assumed_end = 0;  // no assumed usage before the first pass
-        pb.bt.emplace_back(w, &g);
+        pb.batch.emplace_back(w, &g);
       }
     });
     size_t nrq = 0, ntt = 0, naf = 0, nafv = 0;
-    early.clear();
+    t.early.clear();
     for (auto& pb : partBatch) {
       pb.rqb = nrq;
       pb.ttb = ntt;
       pb.afb = naf;
       pb.afvb = nafv;
-      nrq += pb.rq.size();
-      ntt += pb.tt.size();
-      naf += pb.af.size();
-      nafv += pb.afv.size();
-      early.insert(early.end(), pb.early.begin(), pb.early.end());
+      nrq += pb.reqs.size();
+      ntt += pb.taint.size();
+      naf += pb.aff.size();
+      nafv += pb.aff_vals.size();
+      t.early.insert(t.early.end(), pb.early.begin(), pb.early.end());
     }
-    rq.resize(nrq);
-    bt.resize(nrq);
-    tt.resize(ntt);
-    af.resize(naf);
-    afv.resize(nafv);
-    as.clear();
+    t.reqs.resize(nrq);
+    t.batch.resize(nrq);
+    t.taint.resize(ntt);
+    t.aff.resize(naf);
+    t.aff_vals.resize(nafv);
+    t.assumed.clear();
     pool.run_static(W, [&](size_t b, size_t) {
       PartBatch& pb = partBatch[part_of(b)];
       const int32_t ttb = int32_t(pb.ttb), afb = int32_t(pb.afb), afvb = int32_t(pb.afvb);
-      for (size_t k = 0; k < pb.rq.size(); k++) {
-        kueue_tas_eval_req& q = pb.bt[k].second->req;
+      for (size_t k = 0; k < pb.reqs.size(); k++) {
+        kueue_tas_eval_req& q = pb.batch[k].second->req;
         q.taint_table += ttb;
         q.affinity_begin += afb;
         q.affinity_end += afb;
         q.selector_begin += afb;
         q.selector_end += afb;
-        rq[pb.rqb + k] = pb.rq[k];
-        bt[pb.rqb + k] = pb.bt[k];
+        t.reqs[pb.rqb + k] = pb.reqs[k];
+        t.batch[pb.rqb + k] = pb.batch[k];
       }
-      std::copy(pb.tt.begin(), pb.tt.end(), tt.begin() + int64_t(pb.ttb));
-      for (size_t k = 0; k < pb.af.size(); k++) {
-        kueue_tas_affinity_req r = pb.af[k];
+      std::copy(pb.taint.begin(), pb.taint.end(), t.taint.begin() + int64_t(pb.ttb));
+      for (size_t k = 0; k < pb.aff.size(); k++) {
+        kueue_tas_affinity_req r = pb.aff[k];
         r.begin += afvb;
-        af[pb.afb + k] = r;
+        t.aff[pb.afb + k] = r;
       }
-      std::copy(pb.afv.begin(), pb.afv.end(), afv.begin() + int64_t(pb.afvb));
+      std::copy(pb.aff_vals.begin(), pb.aff_vals.end(), t.aff_vals.begin() + int64_t(pb.afvb));
     });
   }
 
@@ -2947,9 +2941,8 @@ struct Evaluator {
   std::vector<kueue_tas_eval_out> balOuts;
   std::vector<int64_t> balOffs;
   bool balReran = false;  // the last balanced_pass ran a device batch of its own
-  int balanced_pass(const std::vector<const kueue_tas_eval_req*>& rq, const std::vector<int32_t>& tt,
-                    const std::vector<kueue_tas_affinity_req>* af, const std::vector<int32_t>* afv,
-                    const std::vector<std::pair<size_t, GroupEval*>>& bt, const int32_t** ent_view) {
+  int balanced_pass(const PassTables& pt, const int32_t** ent_view) {
+    const BatchList& bt = pt.batch;
     const size_t n = bt.size();
     balReran = false;
     balOut.assign(n, BalancedOut{});
@@ -2999,7 +2992,7 @@ struct Evaluator {
         }
         g0 += D;
       }
-      const kueue_tas_eval_req& q = *rq[i];
+      const kueue_tas_eval_req& q = *pt.reqs[i];
       ktas_balanced::Params p;
       p.count = q.count;
       p.sliceSize = q.slice_size;
@@ -3023,12 +3016,13 @@ struct Evaluator {
     for (size_t c0 = 0; c0 < again.size(); c0 += chunk) {  // every request of a call in one device chunk
       const size_t m = std::min(chunk, again.size() - c0);
       balReq.clear();
-      for (size_t k = 0; k < m; k++) balReq.push_back(*rq[again[c0 + k]]);
+      for (size_t k = 0; k < m; k++) balReq.push_back(*pt.reqs[again[c0 + k]]);
       balOuts.resize(m);
       balOffs.resize(m + 1);
-      int rc = kueue_tas_eval_batch(s.ctx, balReq.data(), m, tt.data(), tt.size(), int32_t(s.taintStrings.size()),
-                                    assumed.data(), assumed.size(), af->data(), af->size(), afv->data(), afv->size(),
-                                    balOuts.data(), balOffs.data(), nullptr, 0, nullptr, nullptr);
+      int rc = kueue_tas_eval_batch(s.ctx, balReq.data(), m, pt.taint.data(), pt.taint.size(),
+                                    int32_t(s.taintStrings.size()), pt.assumed.data(), pt.assumed.size(), pt.aff.data(),
+                                    pt.aff.size(), pt.aff_vals.data(), pt.aff_vals.size(), balOuts.data(),
+                                    balOffs.data(), nullptr, 0, nullptr, nullptr);
       for (size_t k = 0; k < m && rc == 0; k++) rc = place(again[c0 + k], k);
       if (rc) {
         snap->err = std::string("balanced placement: ") + kueue_tas_last_error(s.ctx);
@@ -3044,209 +3038,242 @@ struct Evaluator {
   // (SimulateUsageRemoval).
   using Overlay = std::vector<kueue_tas_assumed>;
   const std::vector<Overlay>* base = nullptr;
+
+  // ---- the stages of run(), in its order ----
+  void reset_run(RunState& st) {
+    diag = RunDiag{};
+    st.t_start = st.t_prep = now_ms();
+    st.results.resize(st.wls.size());
+    used.assign(st.wls.size(), 0);
+    ctr_bt = nullptr;
+  }
+
+  // grouping (FindTopologyAssignmentsForFlavor :528-541) and the
+  // findTopologyAssignment prelude (:804-897) per workload, over the host
+  // pool: every workload writes only its own groups; new resource
+  // columns (rare: they reload the snapshot) are added serially between
+  void group_and_compile(RunState& st, bool simulateEmpty, bool regroup) {
+    std::vector<Workload>& wls = st.wls;
+    HostPool& pool = HostPool::get();
+    std::atomic<bool> unknown{false};
+    pool.run_static(wls.size(), [&](size_t b, size_t e) {
+      bool u = false;
+      for (size_t w = b; w < e; w++) {
+        if (wls[w].groups.empty() || regroup) make_groups(wls[w]);
+        u = u || !snap->columns_known(wls[w].podsets);
+      }
+      if (u) unknown.store(true, std::memory_order_relaxed);
+    });
+    bool changed = false;
+    if (unknown.load())
+      for (auto& wl : wls) changed |= snap->ensure_columns_for(wl.podsets);
+    const double t_c = now_ms();
+    diag.detail_ms[RunDiag::kGrouping] += t_c - st.t_start;
+    snap->compile_gen++;
+    std::string perr;
+    std::mutex perr_mu;
+    pool.run_static(wls.size(), [&](size_t b, size_t e) {
+      try {
+        for (size_t w = b; w < e; w++)
+          for (auto& g : wls[w].groups)
+            if (!g.compiled || changed) snap->compile_group_only(g, simulateEmpty);
+      } catch (const std::exception& x) {
+        std::lock_guard<std::mutex> lk(perr_mu);
+        if (perr.empty()) perr = x.what();
+      }
+    });
+    if (!perr.empty()) throw std::runtime_error(perr);
+    diag.detail_ms[RunDiag::kCompile] += now_ms() - t_c;
+  }
+
+  // The pass's tables.  The builders write table offsets into the groups' own
+  // records, so the cached first pass holds only until another build of
+  // pass 0 overwrites them (p0_for = nullptr).
+  PassTables& build_tables(RunState& st, bool precompiled) {
+    const double t_bp = now_ms();
+    PassTables* t = &cur;
+    if (st.pass == 0 && precompiled && !base) {  // no assumed usage yet: reuse the compiled first pass
+      if (p0_for != &st.wls || p0_gen != snap->compile_gen) {
+        build_pass(st, first);
+        p0_for = &st.wls;
+        p0_gen = snap->compile_gen;
+      }
+      t = &first;
+    } else if (st.pass == 0 && !base) {
+      build_pass0_static(st, cur);
+      p0_for = nullptr;
+    } else {
+      build_pass(st, cur);
+      if (st.pass == 0) p0_for = nullptr;
+    }
+    diag.detail_ms[RunDiag::kBuildPass] += now_ms() - t_bp;
+    return *t;
+  }
+
+  void report_early(RunState& st, const PassTables& t) {
+    for (auto& we : t.early) {
+      for (auto* m : we.second->members)
+        set_result(st.results[we.first], used[we.first], m->name, false, nullptr, 0, we.second->early_reason);
+      st.done[we.first] = 1;
+    }
+  }
+
+  // One device batch of the pass's requests; *ent_view: its entries, the
+  // zero-copy view (pinned, strided regions) or the packed copy.
+  int evaluate(const RunState& st, const PassTables& t, const int32_t** ent_view) {
+    const size_t n = t.batch.size();
+    outs.resize(n);
+    offsets.resize(n + 1);
+    taint_counts.resize(n * std::max<size_t>(st.T, 1));
+    res_counts.resize(n * st.R);
+    const bool packed = (snap->cfg.flags & KUEUE_TAS_CFG_PACKED_ENTRIES) != 0;
+    if (packed && entries.size() < 2 * 64 * n) entries.resize(2 * 64 * n);
+    int rc = kueue_tas_eval_batch_ptrs(snap->ctx, t.reqs.data(), n, t.taint.data(), t.taint.size(), int32_t(st.T),
+                                       t.assumed.data(), t.assumed.size(), t.aff.data(), t.aff.size(),
+                                       t.aff_vals.data(), t.aff_vals.size(), outs.data(), offsets.data(),
+                                       packed ? entries.data() : nullptr, packed ? entries.size() / 2 : 0,
+                                       taint_counts.data(), res_counts.data());
+    if (rc == KUEUE_TAS_EOVERFLOW && packed) {
+      entries.resize(size_t(offsets[n]) * 2 + 2);
+      rc = kueue_tas_fetch_entries(snap->ctx, entries.data(), entries.size() / 2);
+    }
+    if (rc) {
+      snap->err = std::string("eval: ") + kueue_tas_last_error(snap->ctx);
+      return rc;
+    }
+    *ent_view = packed ? entries.data() : kueue_tas_last_entries(snap->ctx, nullptr);
+    return 0;
+  }
+
+  // the device layer's diagnostics of the batch of n evals that just ran
+  void collect_device_diag(size_t n) {
+    float t4[4];
+    kueue_tas_last_timings(snap->ctx, t4);
+    for (int k = 0; k < 4; k++) diag.ms[k] += t4[k];
+    float sm[KUEUE_TAS_NUM_STAGES];
+    kueue_tas_last_stage_times(snap->ctx, sm, KUEUE_TAS_NUM_STAGES);
+    for (int k = 0; k < KUEUE_TAS_NUM_STAGES; k++) diag.stage_ms[k] += sm[k];
+    double ht[8];
+    kueue_tas_last_host_times(snap->ctx, ht, 8);
+    for (int k = 0; k < 8; k++) diag.dev_host_ms[k] += ht[k];
+    int64_t st4[4];
+    kueue_tas_last_stats(snap->ctx, st4);
+    for (int k = 0; k < RunDiag::kStagedCols; k++) diag.stats[k] += st4[k];
+    diag.stats[RunDiag::kStagedCols] = std::max(diag.stats[RunDiag::kStagedCols], st4[RunDiag::kStagedCols]);
+    diag.stats[RunDiag::kFillPaths] |= int64_t(kueue_tas_last_fill_paths(snap->ctx));
+    diag.stats[RunDiag::kAliasFills] += kueue_tas_last_alias_fills(snap->ctx);
+    diag.counts[RunDiag::kBatches]++;
+    diag.counts[RunDiag::kEvals] += int64_t(n);
+  }
+
+  int balanced_stage(const PassTables& t, const int32_t** ent_view) {
+    int rc = balanced_pass(t, ent_view);
+    if (rc) return rc;
+    ctr_bt = balReran ? nullptr : &t.batch;  // re-run: the context now holds the balanced re-evaluation
+    ctr_ctx = snap->ctx;
+    ctr_gen = kueue_tas_eval_generation(snap->ctx);
+    return 0;
+  }
+
+  // Every eval of the pass writes only its own workload's results, assumed
+  // usage and done flag, so the evals decode in parallel (the failure-text
+  // caches are filled first: they are shared).
+  void decode(RunState& st, const PassTables& t, const int32_t* ent_view) {
+    snap->reason_order();
+    (void)snap->topology_quoted();
+    std::atomic<int64_t> leaders{0};
+    HostPool::get().run_static(t.batch.size(), [&](size_t i0, size_t i1) {
+      leaders.fetch_add(decode_part(st, t, ent_view, i0, i1), std::memory_order_relaxed);
+    });
+    diag.counts[RunDiag::kLeaderEvals] += leaders.load();
+  }
+
+  // evals [i0, i1) of the batch; returns how many of them have a leader
+  int64_t decode_part(RunState& st, const PassTables& t, const int32_t* ent_view, size_t i0, size_t i1) {
+    std::string reasonBuf;
+    int64_t nlead = 0;
+    for (size_t i = i0; i < i1; i++) {
+      const size_t w = t.batch[i].first;
+      GroupEval& g = *t.batch[i].second;
+      std::vector<PodSetResult>& rs = st.results[w];
+      const kueue_tas_eval_out& o = outs[i];
+      nlead += (g.req.flags & KUEUE_TAS_F_LEADER) ? 1 : 0;
+      const BalancedOut* bo = g.balanced && balOut[i].used ? &balOut[i] : nullptr;
+      if (bo && !bo->reason.empty()) {  // TAS Balanced Placement failure (tas_balanced_placement.go:149-184, :295-314)
+        for (auto* m : g.members) set_result(rs, used[w], m->name, false, nullptr, 0, bo->reason);
+        st.done[w] = 1;
+        continue;
+      }
+      if (!bo && o.status != KUEUE_TAS_ST_OK) {
+        snap->failure_reason(reasonBuf, g, o, taint_counts.data() + i * std::max<size_t>(st.T, 1),
+                             res_counts.data() + i * st.R);
+        for (auto* m : g.members) set_result(rs, used[w], m->name, false, nullptr, 0, reasonBuf);
+        st.done[w] = 1;
+        continue;
+      }
+      const DomainAssignment* e = bo ? bo->workers.data()
+                                     : reinterpret_cast<const DomainAssignment*>(ent_view + size_t(offsets[i]) * 2);
+      const int32_t nw = bo ? int32_t(bo->workers.size()) : o.num_workers;
+      const int32_t nl = bo ? int32_t(bo->leaders.size()) : o.num_leaders;
+      const DomainAssignment* ld = bo ? bo->leaders.data() : e + o.num_workers;
+      // addAssumedUsage (:658-666) only matters for the workload's later groups:
+      // SinglePodRequests x count (no pods term)
+      if (st.pass + 1 < st.wls[w].groups.size()) {
+        auto add = [&](const TASPodSetRequests* tr, const DomainAssignment* ds, int32_t nd) {
+          for (int32_t k = 0; k < nd; k++)
+            for (auto& kv : tr->requestIds)
+              st.assumedBy[w].add(ds[k].leaf, snap->col_of(kv.first), mul64(kv.second, ds[k].count));
+        };
+        add(g.workers, e, nw);
+        if (g.leader) add(g.leader, ld, nl);
+      }
+      static const std::string kEmpty;
+      for (auto* m : g.members) {
+        if (m == g.workers) set_result(rs, used[w], m->name, true, e, size_t(nw), kEmpty);
+        else if (m == g.leader) set_result(rs, used[w], m->name, true, ld, size_t(nl), kEmpty);
+        else set_result(rs, used[w], m->name, false, nullptr, 0, kEmpty);
+      }
+      if (bo)  // the balanced result lives in balOut until the next batch
+        for (size_t k = 0; k < used[w]; k++) rs[k].materialize();
+    }
+    return nlead;
+  }
+
   int run(std::vector<Workload>& wls, bool simulateEmpty, std::vector<std::vector<PodSetResult>>* results,
           bool precompiled = false, const std::vector<Overlay>* base_overlay = nullptr, bool regroup = false) {
     base = base_overlay;
-    ms[0] = ms[1] = ms[2] = ms[3] = 0;
-    for (auto& v : stage_ms) v = 0;
-    for (auto& v : dev_host_ms) v = 0;
-    counts[0] = counts[1] = counts[2] = 0;
-    stats[0] = stats[1] = stats[2] = stats[3] = stats[4] = stats[5] = 0;
-    host_ms[0] = host_ms[1] = host_ms[2] = host_ms[3] = 0;
-    detail_ms[0] = detail_ms[1] = detail_ms[2] = detail_ms[3] = 0;
-    const double t_start = now_ms();
-    double t_prep = t_start;  // start of the current pass's preparation
-    results->resize(wls.size());
-    used.assign(wls.size(), 0);
-    ctr_bt = nullptr;
-    if (!precompiled) {
-      // grouping (FindTopologyAssignmentsForFlavor :528-541) and the
-      // findTopologyAssignment prelude (:804-897) per workload, over the host
-      // pool: every workload writes only its own groups; new resource
-      // columns (rare: they reload the snapshot) are added serially between
-      HostPool& pool = HostPool::get();
-      std::atomic<bool> unknown{false};
-      pool.run_static(wls.size(), [&](size_t b, size_t e) {
-        bool u = false;
-        for (size_t w = b; w < e; w++) {
-          if (wls[w].groups.empty() || regroup) make_groups(wls[w]);
-          u = u || !snap->columns_known(wls[w].podsets);
-        }
-        if (u) unknown.store(true, std::memory_order_relaxed);
-      });
-      bool changed = false;
-      if (unknown.load())
-        for (auto& wl : wls) changed |= snap->ensure_columns_for(wl.podsets);
-      const double t_c = now_ms();
-      detail_ms[0] += t_c - t_start;
-      snap->compile_gen++;
-      std::string perr;
-      std::mutex perr_mu;
-      pool.run_static(wls.size(), [&](size_t b, size_t e) {
-        try {
-          for (size_t w = b; w < e; w++)
-            for (auto& g : wls[w].groups)
-              if (!g.compiled || changed) snap->compile_group_only(g, simulateEmpty);
-        } catch (const std::exception& x) {
-          std::lock_guard<std::mutex> lk(perr_mu);
-          if (perr.empty()) perr = x.what();
-        }
-      });
-      if (!perr.empty()) throw std::runtime_error(perr);
-      detail_ms[1] += now_ms() - t_c;
-    }
+    RunState st{wls, *results};
+    reset_run(st);
+    if (!precompiled) group_and_compile(st, simulateEmpty, regroup);
     int rc = snap->upload();  // (re)load when columns were added
     if (rc) return rc;
-    std::vector<char> done(wls.size(), 0);
-    std::vector<AssumedUsage> assumedBy(wls.size());
+    st.done.assign(wls.size(), 0);
+    st.assumedBy.resize(wls.size());
+    st.T = snap->taintStrings.size();
+    st.R = snap->cols.size();
     size_t maxGroups = 0;
     for (auto& wl : wls) maxGroups = std::max(maxGroups, wl.groups.size());
-    const size_t T = snap->taintStrings.size();
-    const size_t R = snap->cols.size();
-    std::vector<std::pair<size_t, GroupEval*>> early;
-    for (size_t pass = 0; pass < maxGroups; pass++) {
-      const std::vector<const kueue_tas_eval_req*>* rq = &reqs;
-      const std::vector<int32_t>* tt = &taint_table;
-      const std::vector<kueue_tas_affinity_req>* af = &aff;
-      const std::vector<int32_t>* afv = &affv;
-      const std::vector<std::pair<size_t, GroupEval*>>* bt = &batch;
-      const std::vector<std::pair<size_t, GroupEval*>>* ea = &early;
-      const double t_bp = now_ms();
-      if (pass == 0 && precompiled && !base) {  // no assumed usage yet: reuse the compiled first pass
-        if (p0_for != &wls || p0_gen != snap->compile_gen) {
-          build_pass(wls, 0, done, assumedBy, p0_reqs, p0_taint, assumed, p0_aff, p0_affv, p0_batch, p0_early);
-          p0_for = &wls;
-          p0_gen = snap->compile_gen;
-        }
-        rq = &p0_reqs;
-        tt = &p0_taint;
-        af = &p0_aff;
-        afv = &p0_affv;
-        bt = &p0_batch;
-        ea = &p0_early;
-        assumed.clear();
-      } else if (pass == 0 && !base) {
-        build_pass0_static(wls, done, reqs, taint_table, assumed, aff, affv, batch, early);
-        p0_for = nullptr;  // the groups' records now hold this batch's table offsets
-      } else {
-        build_pass(wls, pass, done, assumedBy, reqs, taint_table, assumed, aff, affv, batch, early);
-        if (pass == 0) p0_for = nullptr;
-      }
-      detail_ms[2] += now_ms() - t_bp;
-      for (auto& we : *ea) {
-        for (auto* m : we.second->members)
-          set_result((*results)[we.first], used[we.first], m->name, false, nullptr, 0, we.second->early_reason);
-        done[we.first] = 1;
-      }
-      if (bt->empty()) continue;
-      if (pass > 0)  // the next batch reuses the entries buffer the earlier views point into
+    for (st.pass = 0; st.pass < maxGroups; st.pass++) {
+      PassTables& t = build_tables(st, precompiled);
+      report_early(st, t);
+      if (t.batch.empty()) continue;
+      if (st.pass > 0)  // the next batch reuses the entries buffer the earlier views point into
         for (size_t w = 0; w < wls.size(); w++)
           for (size_t k = 0; k < used[w]; k++) (*results)[w][k].materialize();
       const double t_call = now_ms();
-      host_ms[0] += t_call - t_prep;  // this pass's preparation only
-      const size_t n = bt->size();
-      outs.resize(n);
-      offsets.resize(n + 1);
-      taint_counts.resize(n * std::max<size_t>(T, 1));
-      res_counts.resize(n * R);
-      const bool packed = (snap->cfg.flags & KUEUE_TAS_CFG_PACKED_ENTRIES) != 0;
-      if (packed && entries.size() < 2 * 64 * n) entries.resize(2 * 64 * n);
-      rc = kueue_tas_eval_batch_ptrs(snap->ctx, rq->data(), n, tt->data(), tt->size(), int32_t(T), assumed.data(),
-                                assumed.size(), af->data(), af->size(), afv->data(), afv->size(), outs.data(), offsets.data(), packed ? entries.data() : nullptr,
-                                packed ? entries.size() / 2 : 0, taint_counts.data(), res_counts.data());
-      if (rc == KUEUE_TAS_EOVERFLOW && packed) {
-        entries.resize(size_t(offsets[n]) * 2 + 2);
-        rc = kueue_tas_fetch_entries(snap->ctx, entries.data(), entries.size() / 2);
-      }
-      if (rc) {
-        snap->err = std::string("eval: ") + kueue_tas_last_error(snap->ctx);
-        return rc;
-      }
-      // zero-copy view (pinned, strided regions) or the packed copy
-      const int32_t* ent_view = packed ? entries.data() : kueue_tas_last_entries(snap->ctx, nullptr);
-      float t4[4];
-      kueue_tas_last_timings(snap->ctx, t4);
-      for (int k = 0; k < 4; k++) ms[k] += t4[k];
-      float st[KUEUE_TAS_NUM_STAGES];
-      kueue_tas_last_stage_times(snap->ctx, st, KUEUE_TAS_NUM_STAGES);
-      for (int k = 0; k < KUEUE_TAS_NUM_STAGES; k++) stage_ms[k] += st[k];
-      double ht[8];
-      kueue_tas_last_host_times(snap->ctx, ht, 8);
-      for (int k = 0; k < 8; k++) dev_host_ms[k] += ht[k];
-      int64_t st4[4];
-      kueue_tas_last_stats(snap->ctx, st4);
-      for (int k = 0; k < 3; k++) stats[k] += st4[k];
-      stats[3] = std::max(stats[3], st4[3]);
-      stats[4] |= int64_t(kueue_tas_last_fill_paths(snap->ctx));
-      stats[5] += kueue_tas_last_alias_fills(snap->ctx);
-      rc = balanced_pass(*rq, *tt, af, afv, *bt, &ent_view);  // after the diagnostics: it may run a batch
-      if (rc) return rc;
-      ctr_bt = balReran ? nullptr : bt;  // re-run: the context now holds the balanced re-evaluation
-      ctr_ctx = snap->ctx;
-      ctr_gen = kueue_tas_eval_generation(snap->ctx);
+      diag.host_ms[RunDiag::kPrepare] += t_call - st.t_prep;  // this pass's preparation only
+      const int32_t* ent_view = nullptr;
+      if ((rc = evaluate(st, t, &ent_view))) return rc;
+      collect_device_diag(t.batch.size());  // before the balanced pass: it may run a batch of its own
+      if ((rc = balanced_stage(t, &ent_view))) return rc;
       const double t_decode = now_ms();
-      host_ms[1] += t_decode - t_call;
-      counts[0]++;
-      counts[1] += int64_t(n);
-      // decode: every eval of the pass writes only its own workload's
-      // results, assumed usage and done flag, so the evals decode in parallel
-      // (the failure-text caches are filled first: they are shared)
-      snap->reason_order();
-      (void)snap->topology_quoted();
-      std::atomic<int64_t> leaders{0};
-      HostPool::get().run_static(n, [&](size_t i0, size_t i1) {
-      std::string reasonBuf;
-      int64_t nlead = 0;
-      for (size_t i = i0; i < i1; i++) {
-        const size_t w = (*bt)[i].first;
-        GroupEval& g = *(*bt)[i].second;
-        const kueue_tas_eval_out& o = outs[i];
-        nlead += (g.req.flags & KUEUE_TAS_F_LEADER) ? 1 : 0;
-        const BalancedOut* bo = g.balanced && balOut[i].used ? &balOut[i] : nullptr;
-        if (bo && !bo->reason.empty()) {  // TAS Balanced Placement failure (tas_balanced_placement.go:149-184, :295-314)
-          for (auto* m : g.members) set_result((*results)[w], used[w], m->name, false, nullptr, 0, bo->reason);
-          done[w] = 1;
-          continue;
-        }
-        if (!bo && o.status != KUEUE_TAS_ST_OK) {
-          snap->failure_reason(reasonBuf, g, o, taint_counts.data() + i * std::max<size_t>(T, 1), res_counts.data() + i * R);
-          for (auto* m : g.members) set_result((*results)[w], used[w], m->name, false, nullptr, 0, reasonBuf);
-          done[w] = 1;
-          continue;
-        }
-        const DomainAssignment* e = bo ? bo->workers.data()
-                                       : reinterpret_cast<const DomainAssignment*>(ent_view + size_t(offsets[i]) * 2);
-        const int32_t nw = bo ? int32_t(bo->workers.size()) : o.num_workers;
-        const int32_t nl = bo ? int32_t(bo->leaders.size()) : o.num_leaders;
-        const DomainAssignment* ld = bo ? bo->leaders.data() : e + o.num_workers;
-        // addAssumedUsage (:658-666) only matters for the workload's later groups:
-        // SinglePodRequests x count (no pods term)
-        if (pass + 1 < wls[w].groups.size()) {
-          auto add = [&](const TASPodSetRequests* tr, const DomainAssignment* ds, int32_t nd) {
-            for (int32_t k = 0; k < nd; k++)
-              for (auto& kv : tr->requestIds)
-                assumedBy[w].add(ds[k].leaf, snap->col_of(kv.first), mul64(kv.second, ds[k].count));
-          };
-          add(g.workers, e, nw);
-          if (g.leader) add(g.leader, ld, nl);
-        }
-        static const std::string kEmpty;
-        for (auto* m : g.members) {
-          if (m == g.workers) set_result((*results)[w], used[w], m->name, true, e, size_t(nw), kEmpty);
-          else if (m == g.leader) set_result((*results)[w], used[w], m->name, true, ld, size_t(nl), kEmpty);
-          else set_result((*results)[w], used[w], m->name, false, nullptr, 0, kEmpty);
-        }
-        if (bo)  // the balanced result lives in balOut until the next batch
-          for (size_t k = 0; k < used[w]; k++) (*results)[w][k].materialize();
-      }
-      leaders.fetch_add(nlead, std::memory_order_relaxed);
-      });
-      counts[2] += leaders.load();
-      t_prep = now_ms();
-      host_ms[2] += t_prep - t_decode;
+      diag.host_ms[RunDiag::kEvalCall] += t_decode - t_call;
+      decode(st, t, ent_view);
+      st.t_prep = now_ms();
+      diag.host_ms[RunDiag::kDecode] += st.t_prep - t_decode;
     }
     for (size_t w = 0; w < wls.size(); w++) (*results)[w].resize(used[w]);
-    host_ms[3] = now_ms() - t_start;
+    diag.host_ms[RunDiag::kTotal] = now_ms() - st.t_start;
     return 0;
   }
 };
@@ -3583,9 +3610,7 @@ struct kueue_tas_host {
   uint64_t compiled_gen = 0;  // bumped when the compiled workload set is replaced
   std::unique_ptr<Evaluator> ev;
   std::vector<std::vector<PodSetResult>> last;
-  float ms[4] = {0, 0, 0, 0};
-  int64_t counts[3] = {0, 0, 0};
-  int64_t stats[6] = {0, 0, 0, 0, 0, 0};
+  RunDiag diag;  // of the last kueue_tas_host_run (kept when ev is reset)
   uint64_t compiled_cols = 0;  // FlavorSnapshot::col_gen the compiled workloads were compiled against
   // this rank's shard of the compiled workloads (indices into `compiled`)
   // and its own compiled copies; empty: run_compiled evaluates them all
@@ -4482,8 +4507,8 @@ static int preemption_search(kueue_tas_host* h, const kjson::Node& podsets, cons
     std::vector<std::vector<PodSetResult>> results;
     int rc = ev.run(wls, false, &results, false, &base);
     if (rc) return rc;
-    for (int q = 0; q < 4; q++) eval_ms[q] += ev.host_ms[q];
-    for (int q = 0; q < 6; q++) dev_ms[q] += ev.dev_host_ms[q];
+    for (int q = 0; q < 4; q++) eval_ms[q] += ev.diag.host_ms[q];
+    for (int q = 0; q < 6; q++) dev_ms[q] += ev.diag.dev_host_ms[q];
     fit->resize(base.size());
     for (size_t i = 0; i < base.size(); i++) (*fit)[i] = fits_all(results[i]) ? 1 : 0;
     return 0;
@@ -4806,16 +4831,14 @@ int kueue_tas_host_run(kueue_tas_host* h, uint32_t flags, uint64_t* result_hash)
         }
       });
     }
-    ev.host_ms[2] += now_ms() - t0;
-    ev.host_ms[3] += now_ms() - t0;
-    ev.detail_ms[3] += now_ms() - t0;
+    ev.diag.host_ms[RunDiag::kDecode] += now_ms() - t0;
+    ev.diag.host_ms[RunDiag::kTotal] += now_ms() - t0;
+    ev.diag.detail_ms[RunDiag::kValues] += now_ms() - t0;
   }
-  for (int k = 0; k < KUEUE_TAS_NUM_STAGES; k++) h->stage_accum[k] += ev.stage_ms[k];
+  for (int k = 0; k < KUEUE_TAS_NUM_STAGES; k++) h->stage_accum[k] += ev.diag.stage_ms[k];
   h->accum_runs++;
-  h->accum_fills += ev.stats[2];
-  memcpy(h->ms, ev.ms, sizeof h->ms);
-  memcpy(h->counts, ev.counts, sizeof h->counts);
-  memcpy(h->stats, ev.stats, sizeof h->stats);
+  h->accum_fills += ev.diag.stats[RunDiag::kFillLaunches];
+  h->diag = ev.diag;
   if (result_hash) {
     uint64_t x = 1469598103934665603ull;
     auto mix = [&](uint64_t v) {  // word-wise FNV-1a variant
@@ -4845,13 +4868,13 @@ int kueue_tas_host_run_compiled(kueue_tas_host* h, uint64_t* result_hash) { retu
 
 int kueue_tas_host_last_device_host_times(kueue_tas_host* h, double* ms, int n) {
   if (!h || !h->ev || !ms || n < 0) return KUEUE_TAS_EINVAL;
-  for (int k = 0; k < n && k < 8; k++) ms[k] = h->ev->dev_host_ms[k];
+  for (int k = 0; k < n && k < 8; k++) ms[k] = h->ev->diag.dev_host_ms[k];
   return 0;
 }
 
 int kueue_tas_host_last_stage_times(kueue_tas_host* h, float* ms, int n) {
   if (!h || !h->ev || !ms || n < 0) return KUEUE_TAS_EINVAL;
-  for (int k = 0; k < n && k < KUEUE_TAS_NUM_STAGES; k++) ms[k] = h->ev->stage_ms[k];
+  for (int k = 0; k < n && k < KUEUE_TAS_NUM_STAGES; k++) ms[k] = h->ev->diag.stage_ms[k];
   return 0;
 }
 
@@ -4877,7 +4900,7 @@ int kueue_tas_host_last_eval_profile(kueue_tas_host* h, int32_t* ticks, size_t n
 
 int kueue_tas_host_last_profile(kueue_tas_host* h, double* ms4) {
   if (!h || !h->ev) return KUEUE_TAS_EINVAL;
-  memcpy(ms4, h->ev->host_ms, sizeof h->ev->host_ms);
+  memcpy(ms4, h->ev->diag.host_ms, sizeof h->ev->diag.host_ms);
   return 0;
 }
 
@@ -4908,23 +4931,21 @@ int kueue_tas_host_last_update_detail(kueue_tas_host* h, double* ms, int n) {
 
 int kueue_tas_host_last_host_detail(kueue_tas_host* h, double* ms, int n) {
   if (!h || !h->ev || !ms || n < 0) return KUEUE_TAS_EINVAL;
-  for (int k = 0; k < n && k < 4; k++) ms[k] = h->ev->detail_ms[k];
+  for (int k = 0; k < n && k < 4; k++) ms[k] = h->ev->diag.detail_ms[k];
   return 0;
 }
 
 int kueue_tas_host_last_timings(kueue_tas_host* h, float* ms4, int64_t* counts3) {
   if (!h) return KUEUE_TAS_EINVAL;
-  if (ms4) memcpy(ms4, h->ms, sizeof h->ms);
-  if (counts3) memcpy(counts3, h->counts, sizeof h->counts);
+  if (ms4) memcpy(ms4, h->diag.ms, sizeof h->diag.ms);
+  if (counts3) memcpy(counts3, h->diag.counts, sizeof h->diag.counts);
   return 0;
 }
 
 int kueue_tas_host_last_stats(kueue_tas_host* h, int64_t* stats8) {
   if (!h || !stats8) return KUEUE_TAS_EINVAL;
-  stats8[0] = h->counts[0];
-  stats8[1] = h->counts[1];
-  stats8[2] = h->counts[2];
-  for (int k = 0; k < 5; k++) stats8[3 + k] = h->stats[k];
+  for (int k = 0; k < 3; k++) stats8[k] = h->diag.counts[k];
+  for (int k = 0; k < 5; k++) stats8[3 + k] = h->diag.stats[k];
   return 0;
 }
 
@@ -4932,7 +4953,7 @@ int kueue_tas_host_last_stats_ext(kueue_tas_host* h, int64_t* out, int32_t n) {
   if (!h || !out || n < 0) return KUEUE_TAS_EINVAL;
   int64_t all[9];
   kueue_tas_host_last_stats(h, all);
-  all[8] = h->stats[5];
+  all[8] = h->diag.stats[5];
   for (int k = 0; k < n && k < 9; k++) out[k] = all[k];
   return 0;
 }
@@ -5506,12 +5527,19 @@ int kueue_tas_host_compile_workload(kueue_tas_host* h, const char* podsets_json,
       h->err = s.err;
       return rc;
     }
-    size_t na = 0, nv = 0;
-    for (auto& g : wl.groups) {
-      na += g.aff.size() + g.sel_ext.size();
-      nv += g.aff_vals.size() + g.sel_vals.size();
-    }
+    // one request per group (a copy: g.req keeps its own offsets), one taint
+    // row per group at i * P, no assumed usage
     const size_t P = s.profiles.size();
+    std::vector<kueue_tas_eval_req> rq(wl.groups.size());
+    std::vector<kueue_tas_affinity_req> aff;
+    std::vector<int32_t> aff_vals;
+    for (size_t i = 0; i < wl.groups.size(); i++) {
+      rq[i] = wl.groups[i].req;
+      rq[i].taint_table = int32_t(i * P);
+      rq[i].assumed_begin = rq[i].assumed_end = 0;
+      append_affinity(wl.groups[i], aff, aff_vals, rq[i]);
+    }
+    const size_t na = aff.size(), nv = aff_vals.size();
     *n_groups = wl.groups.size();
     *taint_len = P * wl.groups.size();
     *n_affinity = na;
@@ -5520,31 +5548,13 @@ int kueue_tas_host_compile_workload(kueue_tas_host* h, const char* podsets_json,
     if (reqs_cap < wl.groups.size() || taint_cap < *taint_len || affinity_cap < na || values_cap < nv ||
         (wl.groups.size() && (!reqs || (P && !taint_table))) || (na && !affinity) || (nv && !affinity_values))
       return KUEUE_TAS_EOVERFLOW;
+    std::copy(rq.begin(), rq.end(), reqs);
+    std::copy(aff.begin(), aff.end(), affinity);
+    std::copy(aff_vals.begin(), aff_vals.end(), affinity_values);
     std::string reasons = "[";
-    size_t ka = 0, kv = 0;
     for (size_t i = 0; i < wl.groups.size(); i++) {
       const GroupEval& g = wl.groups[i];
-      kueue_tas_eval_req q = g.req;
-      q.taint_table = int32_t(i * P);
       std::copy(g.taint_row.begin(), g.taint_row.end(), taint_table + i * P);
-      q.assumed_begin = q.assumed_end = 0;
-      q.affinity_begin = int32_t(ka);
-      for (auto r : g.aff) {
-        r.begin += int32_t(kv);
-        affinity[ka++] = r;
-      }
-      q.affinity_end = int32_t(ka);
-      std::copy(g.aff_vals.begin(), g.aff_vals.end(), affinity_values + kv);
-      kv += g.aff_vals.size();
-      q.selector_begin = int32_t(ka);
-      for (auto r : g.sel_ext) {
-        r.begin += int32_t(kv);
-        affinity[ka++] = r;
-      }
-      q.selector_end = int32_t(ka);
-      std::copy(g.sel_vals.begin(), g.sel_vals.end(), affinity_values + kv);
-      kv += g.sel_vals.size();
-      reqs[i] = q;
       if (i) reasons += ",";
       kjson::write_string(reasons, g.early_reason);
     }

@@ -4,6 +4,8 @@ call (KUEUE_TAS_RUN_COMPILE) and of the step that also builds the
 TopologyAssignment values (KUEUE_TAS_RUN_VALUES) are identical and equal the
 oracle's for the whole batch; config C1 (the reference's CPU case) runs as a
 GPU test of its own."""
+import random
+
 import pytest
 
 import oracle_lib
@@ -60,6 +62,42 @@ def test_emulated_run_modes_c3_small(emu_lib):
 def test_emulated_run_modes_c3j_small(emu_lib):
     snap_doc, wls = synth.config_c3j(n_workloads=20, shape=(2, 2, 6), rack_sizes=(5, 19))
     _modes(lambda d: TASFlavorSnapshot(d, lib=emu_lib), snap_doc, wls)
+
+
+def _wide_batch(variant, seed):
+    """A synth.wide_case batch whose workloads carry affinity and nodeSelectors
+    beyond the 8 inline pairs: with RUN_COMPILE the first pass is assembled by
+    the host pool's parts, and every part after the first rebases such records
+    by its offsets into the batch tables."""
+    snap_doc, wls = synth.wide_case(random.Random(seed), variant, n_nodes=300, n_workloads=24)
+    podsets = [ps for wl in wls for ps in wl]
+    assert sum(any(len(ps["nodeSelector"] or {}) > 8 for ps in wl) for wl in wls) >= 2
+    assert any(ps.get("affinity") for ps in podsets)
+    return snap_doc, wls
+
+
+def test_emulated_run_modes_wide_manyres(emu_lib):
+    snap_doc, wls = _wide_batch("manyres", 1)
+    _modes(lambda d: TASFlavorSnapshot(d, lib=emu_lib), snap_doc, wls)
+
+
+def test_emulated_run_modes_c4_small(emu_lib):
+    # two passes: assumed usage and materialized views in every mode
+    snap_doc, wls = synth.config_c4(n_workloads=8, shape=(2, 2, 4, 16))
+    _modes(lambda d: TASFlavorSnapshot(d, lib=emu_lib), snap_doc, wls)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,seed", [("manyres", 1), ("slots", 0)])
+def test_run_modes_wide_on_gpu(variant, seed):
+    snap_doc, wls = _wide_batch(variant, seed)
+    _modes(lambda d: TASFlavorSnapshot(d), snap_doc, wls)
+
+
+@pytest.mark.gpu
+def test_run_modes_c4_on_gpu():
+    snap_doc, wls = synth.config_c4(n_workloads=8, shape=(2, 2, 4, 16))
+    _modes(lambda d: TASFlavorSnapshot(d), snap_doc, wls)
 
 
 @pytest.mark.gpu
