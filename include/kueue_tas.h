@@ -454,6 +454,29 @@ int kueue_tas_admit_table(kueue_tas_ctx* ctx, const int32_t* ps_base, int32_t nu
 int kueue_tas_admit_block(kueue_tas_ctx* ctx, const int32_t* block, size_t row_words, const int64_t* lens,
                           int32_t world, int32_t pods_col, int32_t* ids, int32_t* admitted, size_t cap,
                           size_t* n_workloads, const kueue_tas_delta** deltas, size_t* n_deltas);
+/* kueue_tas_admit_block for a cycle whose entries carry preemption targets:
+ * kueue_tas_admit_targets' semantics (verdict 0 / 1 / 2 in admitted[], the
+ * preempted targets subtracted for the rest of the call and back at its end)
+ * over kueue_tas_admit_block's records.  The target table is
+ * kueue_tas_admit_targets' (target_deltas, target_off[n_targets + 1]); the
+ * entries' lists are keyed by workload id, because the ascending order is
+ * derived on the device: entry e = workload entry_ids[e] (each id at most
+ * once, any order) lists entry_targets[entry_target_off[e] ..
+ * entry_target_off[e + 1]).  The delta list holds the verdict-1 entries'
+ * usage only, in kueue_tas_host_admit_targets' order; after the call
+ * tas_usage is the usage before it plus that list, bit for bit.
+ * KUEUE_TAS_EINVAL, with the snapshot untouched and nothing admitted, for
+ * everything kueue_tas_admit_targets rejects, an entry id outside the
+ * admission table's workloads, given twice, or without a header in the block.
+ * KUEUE_TAS_ELAYOUT / _EHOSTMEM / _EOVERFLOW as kueue_tas_admit_block.  With
+ * n_entries == 0 or every list empty the call is kueue_tas_admit_block's
+ * launch sequence; the path adds no host synchronisation to it. */
+int kueue_tas_admit_block_targets(kueue_tas_ctx* ctx, const int32_t* block, size_t row_words, const int64_t* lens,
+                                  int32_t world, int32_t pods_col, const kueue_tas_delta* target_deltas,
+                                  const int64_t* target_off, size_t n_targets, const int32_t* entry_ids,
+                                  const int64_t* entry_target_off, const int32_t* entry_targets, size_t n_entries,
+                                  int32_t* ids, int32_t* admitted, size_t cap, size_t* n_workloads,
+                                  const kueue_tas_delta** deltas, size_t* n_deltas);
 
 /* ---- v1beta2 compact TopologyAssignment encoding -------------------------
  * V1Beta2From / singleCompactSliceEncoding (pkg/util/tas/tas_assignment.go:
@@ -576,6 +599,30 @@ int kueue_tas_host_apply_deltas(kueue_tas_host* h, const kueue_tas_delta* deltas
 int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t row_words, const int64_t* lens,
                                int32_t world, int32_t* admitted, size_t admitted_cap, size_t* n_workloads,
                                size_t* n_deltas);
+/* kueue_tas_host_admit_block for entries with preemption targets
+ * (kueue_tas_admit_block_targets), the targets in binary form — no JSON on
+ * the call: target t's records are target_deltas[target_off[t] ..
+ * target_off[t + 1]) (the kueue_tas_delta records kueue_tas_host_last_deltas
+ * returned when it was admitted, or kueue_tas_host_usage_deltas of its usage
+ * records; a record whose column is not a column of the snapshot is
+ * KUEUE_TAS_EINVAL), entry e = workload entry_ids[e] lists
+ * entry_targets[entry_target_off[e] .. entry_target_off[e + 1]).  admitted =
+ * (id, verdict 0 / 1 / 2) pairs; the mirror and the delta list as
+ * kueue_tas_host_admit_targets.  A block outside the assignments layout or in
+ * host memory is admitted through the host path with the same targets. */
+int kueue_tas_host_admit_block_targets(kueue_tas_host* h, const int32_t* block, size_t row_words, const int64_t* lens,
+                                       int32_t world, const kueue_tas_delta* target_deltas, const int64_t* target_off,
+                                       size_t n_targets, const int32_t* entry_ids, const int64_t* entry_target_off,
+                                       const int32_t* entry_targets, size_t n_entries, int32_t* admitted,
+                                       size_t admitted_cap, size_t* n_workloads, size_t* n_deltas);
+/* The delta records of usage-record JSON ([{"values", "singlePodRequests",
+ * "count"}, ...]) exactly as kueue_tas_host_admit_targets forms them for a
+ * target: single x count per resource plus pods:count, in resource-name
+ * order, records for unknown domains skipped.  Resources without a column get
+ * one (the next upload reloads).  *len = the record count;
+ * KUEUE_TAS_EOVERFLOW when cap is short (nothing copied). */
+int kueue_tas_host_usage_deltas(kueue_tas_host* h, const char* usage_json, kueue_tas_delta* buf, size_t cap,
+                                size_t* len);
 
 /* Every result of the last run_compiled as {"results": [[{"name",
  * "assignment","reason"}...] per compiled workload]} (kueue_tas_free). */

@@ -201,8 +201,24 @@ int kueue_tas_host_last_admit_stats(kueue_tas_host* h, int64_t* out3);
 // The last kueue_tas_admit / kueue_tas_admit_targets: [0] runs of target-free
 // entries that went through the pass, [1] admit_step_kernel launches, [2]
 // kernel launches in all (a call without targets: 1, 0, the pass's).
+// kueue_tas_admit_block(_targets) reports the same three for its admission
+// stage ([2] with admit_block_runs_kernel); the kernels that build the
+// block's records, lists (admit_block_entries_kernel) and deltas are not
+// counted, with or without targets.
 int kueue_tas_last_admit_launches(kueue_tas_ctx* ctx, int64_t* out3);
 int kueue_tas_host_last_admit_launches(kueue_tas_host* h, int64_t* out3);
+// Where the last kueue_tas_host_admit_block / _admit_block_targets admitted:
+// 1 from the block on the device (kueue_tas_admit_block(_targets)), 0 through
+// the host path (a block outside the assignments layout or in host memory),
+// -1 before the first call.  A call that failed (anything but
+// KUEUE_TAS_EOVERFLOW) admitted nothing and leaves the value as it was.
+int kueue_tas_host_last_admit_block_path(kueue_tas_host* h);
+// The generation of the snapshot's resource columns: it moves whenever the
+// column set changes, which renumbers the columns that kueue_tas_delta
+// records name.  A caller that keeps delta records across calls (a target
+// table for kueue_tas_host_admit_block_targets) compares it to know they
+// still name the snapshot's columns.  0 without a snapshot.
+uint64_t kueue_tas_host_column_generation(kueue_tas_host* h);
 
 #ifdef __cplusplus
 }

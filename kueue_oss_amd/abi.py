@@ -150,4 +150,15 @@ def bind_device_layer(lib):
                                             c.c_size_t, c.c_int32, P(Delta), P(c.c_int64), c.c_size_t, P(c.c_int32),
                                             P(c.c_int64), P(c.c_int32)]
     lib.kueue_tas_admit_targets.restype = c.c_int
+    lib.kueue_tas_admit_table.argtypes = [c.c_void_p, P(c.c_int32), c.c_int32, P(c.c_int32), P(FitsTerm), c.c_size_t]
+    lib.kueue_tas_admit_table.restype = c.c_int
+    lib.kueue_tas_admit_block.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, P(c.c_int64), c.c_int32, c.c_int32,
+                                          P(c.c_int32), P(c.c_int32), c.c_size_t, P(c.c_size_t), P(P(Delta)),
+                                          P(c.c_size_t)]
+    lib.kueue_tas_admit_block.restype = c.c_int
+    lib.kueue_tas_admit_block_targets.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, P(c.c_int64), c.c_int32, c.c_int32,
+                                                  P(Delta), P(c.c_int64), c.c_size_t, P(c.c_int32), P(c.c_int64),
+                                                  P(c.c_int32), c.c_size_t, P(c.c_int32), P(c.c_int32), c.c_size_t,
+                                                  P(c.c_size_t), P(P(Delta)), P(c.c_size_t)]
+    lib.kueue_tas_admit_block_targets.restype = c.c_int
     return lib

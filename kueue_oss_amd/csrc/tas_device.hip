@@ -1672,9 +1672,141 @@ int kueue_tas_admit_table(kueue_tas_ctx* c, const int32_t* ps_base, int32_t num_
   return KUEUE_TAS_OK;
 }
 
-int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_words, const int64_t* lens,
-                          int32_t world, int32_t pods_col, int32_t* ids, int32_t* admitted, size_t cap,
-                          size_t* n_workloads, const kueue_tas_delta** deltas, size_t* n_deltas) {
+// kueue_tas_admit_block_targets' extra arguments (null: kueue_tas_admit_block):
+// the target table of kueue_tas_admit_targets and the entries' lists keyed by
+// workload id.
+struct AdmitBlockTargets {
+  const kueue_tas_delta* deltas;
+  const int64_t* off;  // [T + 1] CSR into deltas
+  size_t T;
+  const int32_t* entry_ids;      // [E] each id at most once, any order
+  const int64_t* entry_off;      // [E + 1] CSR into entry_targets
+  const int32_t* entry_targets;  // target ids
+  size_t E;
+};
+
+// What kueue_tas_admit_targets rejects, and an entry id out of range.  An id
+// given twice or without a header in the block shows after the first
+// synchronise: on the device's claims (admit_block_entries_kernel), or for
+// ids with empty lists only, on the headers' flags.
+static int admit_block_targets_check(kueue_tas_ctx* c, const AdmitBlockTargets& bt, int W) {
+  if ((bt.T && !bt.off) || (bt.E && (!bt.entry_ids || !bt.entry_off))) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+  if (bt.T > size_t(INT32_MAX) || bt.E > size_t(INT32_MAX)) return fail(c, KUEUE_TAS_EINVAL, "too many targets");
+  if (bt.T && bt.off[0] != 0) return fail(c, KUEUE_TAS_EINVAL, "target offsets");
+  for (size_t t = 0; t < bt.T; t++)
+    if (bt.off[t + 1] < bt.off[t]) return fail(c, KUEUE_TAS_EINVAL, "target offsets not monotone");
+  const size_t nd = bt.T ? size_t(bt.off[bt.T]) : 0;
+  if (nd && !bt.deltas) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+  for (size_t j = 0; j < nd; j++) {
+    const kueue_tas_delta& x = bt.deltas[j];
+    if (x.leaf < -1 || x.leaf >= c->snap.N) return fail(c, KUEUE_TAS_EINVAL, "target record leaf out of range");
+    if (x.col < 0 || x.col >= c->snap.R) return fail(c, KUEUE_TAS_EINVAL, "target record column out of range");
+  }
+  if (!bt.E) return KUEUE_TAS_OK;
+  if (bt.entry_off[0] != 0) return fail(c, KUEUE_TAS_EINVAL, "entry target offsets");
+  for (size_t e = 0; e < bt.E; e++)
+    if (bt.entry_off[e + 1] < bt.entry_off[e]) return fail(c, KUEUE_TAS_EINVAL, "entry target offsets not monotone");
+  if (bt.entry_off[bt.E] > int64_t(INT32_MAX)) return fail(c, KUEUE_TAS_EINVAL, "too many targets");
+  if (bt.entry_off[bt.E] && !bt.entry_targets) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+  std::vector<int64_t> last(bt.entry_off[bt.E] ? bt.T : 0, -1);  // the entry that listed the target last
+  for (size_t e = 0; e < bt.E; e++) {
+    const int32_t g = bt.entry_ids[e];
+    if (g < 0 || g >= W) return fail(c, KUEUE_TAS_EINVAL, "entry id out of range");
+    for (int64_t k = bt.entry_off[e]; k < bt.entry_off[e + 1]; k++) {
+      const int32_t t = bt.entry_targets[k];
+      if (t < 0 || size_t(t) >= bt.T) return fail(c, KUEUE_TAS_EINVAL, "target id out of range");
+      if (last[size_t(t)] == int64_t(e)) return fail(c, KUEUE_TAS_EINVAL, "target listed twice by one entry");
+      last[size_t(t)] = int64_t(e);
+    }
+  }
+  return KUEUE_TAS_OK;
+}
+
+// admit_targets_run over the block path's device arrays: the records, the
+// absolute record -> workload map and the offsets are at layout L (`d`), the
+// compiled terms in c->d_adm_terms, the target table and the per-position
+// lists behind it.  wl_off: the host's copy of the offsets (read when a run
+// goes through the pass: its record range sizes the launches).  The pass
+// runs' bounds are uploaded and admit_block_runs_kernel writes their relative
+// offsets and maps; the verdicts stay on the device for the delta kernels.
+static int admit_block_targets_run(kueue_tas_ctx* c, const AdmitLayout& L, uint8_t* d, const std::vector<AdmitSeg>& segs,
+                                   size_t n_pass, const int64_t* wl_off, size_t n_wl, int32_t pods_col, bool exact,
+                                   size_t T, uint8_t* h_bnd, uint8_t* d_td8, uint8_t* d_toff8, uint8_t* d_etg8,
+                                   uint8_t* d_eoff8, uint8_t* d_pre8, size_t pwords, uint8_t* d_bnd8, uint8_t* d_roff8,
+                                   uint8_t* d_rel8) {
+  const auto* d_reqs = reinterpret_cast<const kueue_tas_fits_req*>(d);
+  const kueue_tas_fits_term* d_terms = c->d_adm_terms.p;
+  const auto* d_off = reinterpret_cast<const int64_t*>(d + L.o_off);
+  const auto* d_td = reinterpret_cast<const kueue_tas_delta*>(d_td8);
+  const auto* d_toff = reinterpret_cast<const int64_t*>(d_toff8);
+  auto* d_pre = reinterpret_cast<uint32_t*>(d_pre8);
+  int32_t* d_out = reinterpret_cast<int32_t*>(d + L.o_out);
+  std::vector<size_t> roff_at(segs.size(), 0);
+  if (n_pass) {
+    int64_t* bnd = reinterpret_cast<int64_t*>(h_bnd);
+    size_t ro = 0, k = 0, widest = 1;
+    for (size_t q = 0; q < segs.size(); q++) {
+      const AdmitSeg& sg = segs[q];
+      if (!sg.pass) continue;
+      roff_at[q] = ro;
+      bnd[3 * k] = int64_t(sg.a);
+      bnd[3 * k + 1] = int64_t(sg.b);
+      bnd[3 * k + 2] = int64_t(ro);
+      ro += sg.b - sg.a + 1;
+      k++;
+      widest = std::max({widest, sg.b - sg.a + 1, size_t(wl_off[sg.b] - wl_off[sg.a])});
+    }
+    HIPCHK(c, hipMemcpyAsync(d_bnd8, bnd, n_pass * 24, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(admit_block_runs_kernel, dim3(unsigned(std::min<size_t>((widest + 255) / 256, 64)),
+                                                     unsigned(std::min<size_t>(n_pass, 65535))),
+                       dim3(256), 0, c->stream, reinterpret_cast<const int64_t*>(d_bnd8), int(n_pass), d_off,
+                       reinterpret_cast<const int32_t*>(d + L.o_recwl), reinterpret_cast<int64_t*>(d_roff8),
+                       reinterpret_cast<int32_t*>(d_rel8));
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemsetAsync(d_pre, 0, admit_al(pwords * 4), c->stream));
+  for (size_t q = 0; q < segs.size(); q++) {
+    const AdmitSeg& sg = segs[q];
+    if (sg.pass) {
+      const size_t r0 = size_t(wl_off[sg.a]);
+      const AdmitView v{d_reqs + r0,
+                        reinterpret_cast<const int32_t*>(d_rel8) + r0,
+                        reinterpret_cast<const int64_t*>(d_roff8) + roff_at[q],
+                        reinterpret_cast<int32_t*>(d + L.o_fit0) + sg.a,
+                        d_out + sg.a,
+                        reinterpret_cast<AdmitRec*>(d + L.o_recs) + r0,
+                        reinterpret_cast<int32_t*>(d + L.o_dep) + sg.a};
+      const int rc = admit_run_view(c, L, d, v, d_terms, size_t(wl_off[sg.b]) - r0, sg.b - sg.a, pods_col, exact);
+      if (rc) return rc;
+    } else {
+      hipLaunchKernelGGL(admit_step_kernel, dim3(1), dim3(1024), 0, c->stream, c->snap, c->d_usage.p,
+                         c->d_usage_present.p, d_reqs, d_terms, d_off, int(sg.a), int(sg.b), pods_col, d_td, d_toff,
+                         reinterpret_cast<const int32_t*>(d_etg8), reinterpret_cast<const int64_t*>(d_eoff8), d_pre,
+                         d_out);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(admit_restore_kernel, dim3(unsigned(std::min<size_t>((T + 3) / 4, 1024))), dim3(256), 0, c->stream,
+                     c->d_usage.p, c->snap.N, d_td, d_toff, int(T), d_pre);
+  HIPCHK(c, hipGetLastError());
+  // the diagnostics words are the last run's (admit_targets_run)
+  if (segs.empty() || !segs.back().pass) HIPCHK(c, hipMemsetAsync(d_out + n_wl, 0, 12, c->stream));
+  c->admit_launches[0] = int64_t(n_pass);
+  c->admit_launches[1] = int64_t(segs.size() - n_pass);
+  c->admit_launches[2] += int64_t(segs.size() - n_pass) + 1 + (n_pass ? 1 : 0);  // + the passes' (admit_run_view)
+  return KUEUE_TAS_OK;
+}
+
+// kueue_tas_admit_block, and with `bt` kueue_tas_admit_block_targets: the
+// records, the verdicts' D2H and the delta list are the same; with targets
+// the id-keyed lists become per-position ones on the device
+// (admit_block_entries_kernel, its bitmap and error bits in the first D2H),
+// the host cuts the list into runs as admit_targets_run does, and the runs'
+// relative maps come from admit_block_runs_kernel.
+static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_words, const int64_t* lens,
+                            int32_t world, int32_t pods_col, int32_t* ids, int32_t* admitted, size_t cap,
+                            size_t* n_workloads, const kueue_tas_delta** deltas, size_t* n_deltas,
+                            const AdmitBlockTargets* bt) {
   if (!c) return KUEUE_TAS_EINVAL;
   if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
   if (!block || !lens || !ids || !admitted || !n_workloads || !deltas || !n_deltas || world < 1)
@@ -1682,6 +1814,13 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
   if (world > kAdmitMaxRows) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: more rows than supported");
   if (c->adm_W < 0) return fail(c, KUEUE_TAS_EINVAL, "admit block: no admission table (kueue_tas_admit_table)");
   if (pods_col < -1 || pods_col >= c->snap.R) return fail(c, KUEUE_TAS_EINVAL, "pods column out of range");
+  if (bt) {
+    const int rc = admit_block_targets_check(c, *bt, c->adm_W);
+    if (rc) return rc;
+  }
+  // some entry lists a target: the targets path; ids given with empty lists
+  // only: kueue_tas_admit_block's launches, the ids checked against the headers
+  const bool tgt = bt && bt->E && bt->entry_off[bt->E] > 0, chk = bt && bt->E && !tgt;
   AdmitRows rows{};
   rows.row_words = int64_t(row_words);
   rows.world = world;
@@ -1709,12 +1848,46 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
                o_ids = o_nd + admit_al(size_t(W) * 4), o_hdr = o_ids + admit_al(size_t(W) * 4),
                o_tot = o_hdr + 256, o_blk = o_tot + admit_al(KUEUE_TAS_MAX_COLS * 16),
                nblk = (std::max<size_t>(Q, 1) + 255) / 256, o_dl = o_blk + admit_al(nblk * 4);
-  HIPCHK(c, c->d_fits.ensure(o_dl + 16));
+  // with targets, behind it: the target table and the id-keyed lists
+  // (uploaded), the positions' claims and the carries-targets bitmap (zeroed),
+  // the per-position lists, the preempted bitmap, the pass runs' bounds, their
+  // relative offsets and record -> workload map
+  const size_t T = tgt ? bt->T : 0, E = tgt ? bt->E : 0, ntd = tgt ? size_t(bt->off[T]) : 0,
+               ne = tgt ? size_t(bt->entry_off[E]) : 0, pwords = (T + 31) / 32,
+               hwords = (size_t(W) + 1023) / 1024 * 32, max_runs = size_t(W) / 2 + 2;
+  const size_t x_td = admit_al(o_dl + 16), x_toff = x_td + admit_al(ntd * sizeof(kueue_tas_delta)),
+               x_eid = x_toff + admit_al((T + 1) * 8), x_eto = x_eid + admit_al(E * 4),
+               x_etl = x_eto + admit_al((E + 1) * 8), x_up = x_etl + admit_al(ne * 4), x_entof = x_up,
+               x_has = x_entof + admit_al(size_t(W) * 4), x_eoff = x_has + admit_al(hwords * 4),
+               x_etg = x_eoff + admit_al((size_t(W) + 1) * 8), x_pre = x_etg + admit_al(ne * 4),
+               x_bnd = x_pre + admit_al(pwords * 4), x_roff = x_bnd + admit_al(max_runs * 24),
+               x_rel = x_roff + admit_al((size_t(W) + max_runs + 1) * 8),
+               x_end = x_rel + admit_al(std::max<size_t>(Q, 1) * 4);
+  HIPCHK(c, c->d_fits.ensure(tgt ? x_end : o_dl + 16));
   uint8_t* d = c->d_fits.p;
   int32_t* hdr = reinterpret_cast<int32_t*>(d + o_hdr);  // [0] workloads [1] records [2] deltas [3] errors [4] negative
+                                                         // [5] entry errors (AdmitEntryErr)
+  // pinned host words: the plain call's, then the bitmap, the workload offsets (int64) and, for ids given
+  // with empty lists only, the headers' flags
+  const size_t a_has = (size_t(W) + 3 + 64 + KUEUE_TAS_MAX_COLS * 4 + 1) / 2 * 2, a_off = a_has + hwords,
+               a_flag = a_off + 2 * (size_t(W) + 1), a_end = a_flag + size_t(W);
+  HIPCHK(c, c->h_admit.reserve(bt ? a_end : size_t(W) + 3 + 64 + KUEUE_TAS_MAX_COLS * 4));
+  // pinned staging: the exact flag and the totals first (below), then the uploads of the targets path
+  const size_t hs_x = admit_al(8 + KUEUE_TAS_MAX_COLS * 8);
+  if (tgt) HIPCHK(c, c->h_stage.ensure(hs_x + std::max(x_up - x_td, admit_al(max_runs * 24))));
   HIPCHK(c, hipMemsetAsync(d + o_flag, 0, size_t(W) * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(d + o_hdr, 0, 256 + admit_al(KUEUE_TAS_MAX_COLS * 16), c->stream));
   const double t0 = wall_ms();
+  if (tgt) {
+    uint8_t* h = c->h_stage.p + hs_x;
+    if (ntd) memcpy(h, bt->deltas, ntd * sizeof(kueue_tas_delta));
+    memcpy(h + (x_toff - x_td), bt->off, (T + 1) * 8);
+    memcpy(h + (x_eid - x_td), bt->entry_ids, E * 4);
+    memcpy(h + (x_eto - x_td), bt->entry_off, (E + 1) * 8);
+    memcpy(h + (x_etl - x_td), bt->entry_targets, ne * 4);
+    HIPCHK(c, hipMemcpyAsync(d + x_td, h, x_up - x_td, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d + x_entof, 0, x_eoff - x_entof, c->stream));
+  }
   if (maxq > 0) {
     hipLaunchKernelGGL(admit_block_headers_kernel, dim3(unsigned((maxq + 255) / 256), unsigned(world)), dim3(256), 0,
                        c->stream, block, rows, W, reinterpret_cast<int32_t*>(d + o_flag),
@@ -1726,15 +1899,51 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
                      reinterpret_cast<int32_t*>(d + o_ids), reinterpret_cast<int64_t*>(d + L.o_off),
                      reinterpret_cast<int32_t*>(d + L.o_fit0), hdr);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, c->h_admit.reserve(size_t(W) + 3 + 64 + KUEUE_TAS_MAX_COLS * 4));
   int32_t* hh = c->h_admit.p;
-  HIPCHK(c, hipMemcpyAsync(hh, hdr, 16, hipMemcpyDeviceToHost, c->stream));
+  if (tgt) {  // the lists by position, their bitmap and error bits: back in the D2H that reads hdr
+    hipLaunchKernelGGL(admit_block_entries_kernel, dim3(1), dim3(1024), 0, c->stream, hdr,
+                       reinterpret_cast<const int32_t*>(d + o_ids), reinterpret_cast<const int32_t*>(d + x_eid),
+                       reinterpret_cast<const int64_t*>(d + x_eto), reinterpret_cast<const int32_t*>(d + x_etl), int(E),
+                       reinterpret_cast<int32_t*>(d + x_entof), reinterpret_cast<int64_t*>(d + x_eoff),
+                       reinterpret_cast<int32_t*>(d + x_etg), reinterpret_cast<uint32_t*>(d + x_has), hdr + 5);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hh + a_has, d + x_has, hwords * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (chk) HIPCHK(c, hipMemcpyAsync(hh + a_flag, d + o_flag, size_t(W) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hh, hdr, tgt ? 32 : 16, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int32_t n_wl = hh[0], n = hh[1];
   if (hh[3] & (ABE_DUP | ABE_LAYOUT | ABE_ID)) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: not the assignments layout");
+  if (tgt && (hh[5] & AEE_ABSENT)) return fail(c, KUEUE_TAS_EINVAL, "entry id without a header in the block");
+  if (tgt && (hh[5] & AEE_DUP)) return fail(c, KUEUE_TAS_EINVAL, "entry id given twice");
+  if (chk)
+    for (size_t e = 0; e < bt->E; e++) {  // (a flag is 1 or 2 for a header; -1 marks an id seen here)
+      int32_t& f = hh[a_flag + size_t(bt->entry_ids[e])];
+      if (f < 0) return fail(c, KUEUE_TAS_EINVAL, "entry id given twice");
+      if (!f) return fail(c, KUEUE_TAS_EINVAL, "entry id without a header in the block");
+      f = -1;
+    }
   *n_workloads = size_t(n_wl);
   if (cap < size_t(n_wl)) return KUEUE_TAS_EOVERFLOW;
   const size_t nwl = size_t(n_wl), nr = size_t(n);
+  // the ordered list cut as admit_targets_run cuts it, by the positions' bitmap
+  std::vector<AdmitSeg> segs;
+  size_t n_pass = 0;
+  if (tgt) {
+    const uint32_t* has = reinterpret_cast<const uint32_t*>(hh + a_has);
+    auto carries = [&](size_t w) { return (has[w >> 5] >> (w & 31)) & 1u; };
+    const size_t min_run = size_t(std::max(c->knobs.admit_step_run, 1));
+    for (size_t w = 0; w < nwl;) {
+      size_t e = w;
+      while (e < nwl && !carries(e)) e++;  // [w, e): target-free
+      const bool pass = e - w >= min_run;
+      if (e == w) e = w + 1;  // a target entry
+      if (!pass && !segs.empty() && !segs.back().pass) segs.back().b = e;
+      else segs.push_back({pass, w, e});
+      w = e;
+    }
+    for (const AdmitSeg& sg : segs) n_pass += sg.pass ? 1 : 0;
+  }
   if (nwl) {
     hipLaunchKernelGGL(admit_block_records_kernel, dim3(unsigned((nwl + 3) / 4)), dim3(256), 0, c->stream, block,
                        c->snap.N, W, reinterpret_cast<const int32_t*>(d + o_ids), reinterpret_cast<const int64_t*>(d + L.o_off),
@@ -1747,6 +1956,8 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
   }
   HIPCHK(c, hipMemcpyAsync(hh, hdr, 32, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(hh + 8, d + o_tot, KUEUE_TAS_MAX_COLS * 16, hipMemcpyDeviceToHost, c->stream));
+  if (n_pass)  // the runs' record ranges (the pass's launch sizes) are the host's to know
+    HIPCHK(c, hipMemcpyAsync(hh + a_off, d + L.o_off, (nwl + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int32_t errs = hh[3];
   if (errs & ABE_LAYOUT) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: not the assignments layout");
@@ -1769,8 +1980,15 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
   HIPCHK(c, hipMemcpyAsync(d + L.o_total, ht, KUEUE_TAS_MAX_COLS * 8, hipMemcpyHostToDevice, c->stream));
   c->admit_launches[0] = 1;
   c->admit_launches[1] = c->admit_launches[2] = 0;
-  const int rc = admit_run(c, L, d, c->d_adm_terms.p, nr, nwl, pods_col, exact);
-  if (rc) return rc;
+  if (tgt) {
+    const int rc = admit_block_targets_run(c, L, d, segs, n_pass, reinterpret_cast<const int64_t*>(hh + a_off), nwl,
+                                           pods_col, exact, T, c->h_stage.p + hs_x, d + x_td, d + x_toff, d + x_etg,
+                                           d + x_eoff, d + x_pre, pwords, d + x_bnd, d + x_roff, d + x_rel);
+    if (rc) return rc;
+  } else {
+    const int rc = admit_run(c, L, d, c->d_adm_terms.p, nr, nwl, pods_col, exact);
+    if (rc) return rc;
+  }
   // the admitted workloads' deltas on the device, in the host path's order
   const int32_t* adm_d = reinterpret_cast<const int32_t*>(d + L.o_out);
   const size_t nb = (std::max<size_t>(nr, 1) + 255) / 256;
@@ -1806,6 +2024,24 @@ int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_wor
   *n_deltas = ndl;
   c->admit_block_ms = wall_ms() - t0;
   return KUEUE_TAS_OK;
+}
+
+int kueue_tas_admit_block(kueue_tas_ctx* c, const int32_t* block, size_t row_words, const int64_t* lens,
+                          int32_t world, int32_t pods_col, int32_t* ids, int32_t* admitted, size_t cap,
+                          size_t* n_workloads, const kueue_tas_delta** deltas, size_t* n_deltas) {
+  return admit_block_impl(c, block, row_words, lens, world, pods_col, ids, admitted, cap, n_workloads, deltas, n_deltas,
+                          nullptr);
+}
+
+int kueue_tas_admit_block_targets(kueue_tas_ctx* c, const int32_t* block, size_t row_words, const int64_t* lens,
+                                  int32_t world, int32_t pods_col, const kueue_tas_delta* target_deltas,
+                                  const int64_t* target_off, size_t n_targets, const int32_t* entry_ids,
+                                  const int64_t* entry_target_off, const int32_t* entry_targets, size_t n_entries,
+                                  int32_t* ids, int32_t* admitted, size_t cap, size_t* n_workloads,
+                                  const kueue_tas_delta** deltas, size_t* n_deltas) {
+  const AdmitBlockTargets bt{target_deltas, target_off, n_targets, entry_ids, entry_target_off, entry_targets, n_entries};
+  return admit_block_impl(c, block, row_words, lens, world, pods_col, ids, admitted, cap, n_workloads, deltas, n_deltas,
+                          &bt);
 }
 
 // The admission pass over the records in c->d_fits (layout L): phase 1

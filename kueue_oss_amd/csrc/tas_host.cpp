@@ -3619,6 +3619,7 @@ struct kueue_tas_host {
   std::vector<Workload>& active() { return shard_ids.empty() ? compiled : shard; }
   std::vector<kueue_tas_delta> last_deltas;  // usage deltas the last kueue_tas_host_admit applied
   double admit_ms[3] = {0, 0, 0};            // last admit: host prep, kueue_tas_admit, delta list
+  int admit_block_path = -1;                 // last kueue_tas_host_admit_block(_targets): 1 on the device, 0 the host path
   // admit's working storage (kept between rounds)
   std::vector<int32_t> admit_seen, admit_ids, admit_adm;
   std::array<uint64_t, 3> admit_table_key{0, 0, 0};  // (compiled set, compile_gen, col_gen) of the device admission table
@@ -5025,28 +5026,62 @@ int kueue_tas_host_last_assignments(kueue_tas_host* h, int32_t* buf, size_t cap,
 // ComputeTASNetUsage builds them, flavorassigner.go:94-130: per assigned
 // domain, the PodSet's single-pod requests and the domain's count).  The
 // device applies the usage (kueue_tas_admit); the host mirror follows.
-// With targets_json (kueue_tas_host_admit_targets): the preemptable
-// workloads' usage becomes delta records as update_usage forms them, the
-// entries' target lists follow the ascending ids, and the device decides the
-// three-valued verdicts (kueue_tas_admit_targets).
-static int host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, const char* targets_json, int32_t* admitted,
+// With targets (kueue_tas_host_admit_targets' JSON and
+// kueue_tas_host_admit_block_targets' arrays both arrive here in the binary
+// form): the entries' target lists follow the ascending ids, and the device
+// decides the three-valued verdicts (kueue_tas_admit_targets).
+struct HostAdmitTargets {
+  const kueue_tas_delta* deltas;  // the preemptable workloads' usage as delta records
+  const int64_t* off;             // [T + 1] CSR into deltas
+  size_t T;
+  const int32_t* entry_ids;      // [E] workload ids
+  const int64_t* entry_off;      // [E + 1] CSR into entry_targets
+  const int32_t* entry_targets;  // target indices
+  size_t E;
+};
+
+// RemoveUsage's records of one workload's usage, as update_usage forms them
+// (single x count per resource and pods:count, in resource-name order; a
+// domain that is no leaf of the snapshot is skipped).
+static void usage_to_deltas(const FlavorSnapshot& s, const std::vector<FlavorSnapshot::DomainUsage>& us,
+                            std::vector<kueue_tas_delta>& td) {
+  for (auto& u : us) {
+    const int32_t leaf = s.leafById.find(u.id);
+    if (leaf < 0) continue;
+    Requests tot;
+    for (auto& kv : u.single) tot[kv.first] = mul64(kv.second, u.count);
+    tot["pods"] = add64(tot["pods"], u.count);
+    for (auto& kv : tot) {
+      const auto col = s.colByName.find(kv.first);
+      if (col == s.colByName.end()) throw std::runtime_error("admit: target resource without a column");
+      td.push_back({leaf, col->second, kv.second});
+    }
+  }
+}
+
+// The binary form's own checks (the device layer judges the rest): the
+// arrays present, a target record's column a column of the snapshot.
+static void check_host_targets(const FlavorSnapshot& s, const HostAdmitTargets& tg) {
+  if ((tg.T && !tg.off) || (tg.E && (!tg.entry_ids || !tg.entry_off))) throw std::runtime_error("admit: null targets argument");
+  if (tg.T && tg.off[0] != 0) throw std::runtime_error("admit: target offsets");
+  for (size_t t = 0; t < tg.T; t++)
+    if (tg.off[t + 1] < tg.off[t]) throw std::runtime_error("admit: target offsets not monotone");
+  const size_t nd = tg.T ? size_t(tg.off[tg.T]) : 0;
+  if (nd && !tg.deltas) throw std::runtime_error("admit: null targets argument");
+  for (size_t j = 0; j < nd; j++)
+    if (tg.deltas[j].col < 0 || size_t(tg.deltas[j].col) >= s.cols.size())
+      throw std::runtime_error("admit: target record column out of range");
+  if (tg.E && tg.entry_off[0] != 0) throw std::runtime_error("admit: entry target offsets");
+  for (size_t e = 0; e < tg.E; e++)
+    if (tg.entry_off[e + 1] < tg.entry_off[e]) throw std::runtime_error("admit: entry target offsets not monotone");
+  if (tg.E && tg.entry_off[tg.E] && !tg.entry_targets) throw std::runtime_error("admit: null targets argument");
+}
+
+static int host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, const HostAdmitTargets* tg, int32_t* admitted,
                       size_t admitted_cap, size_t* n_workloads, size_t* n_deltas) {
   if (!h || !h->snap || !h->err.empty() || (len && !recs) || len % 4 || !n_workloads) return KUEUE_TAS_EINVAL;
   try {
-    std::vector<std::vector<FlavorSnapshot::DomainUsage>> tgUsage;  // per preemptable workload
-    std::vector<std::pair<int32_t, std::vector<int32_t>>> tgLists;  // (entry id, workload indices)
-    if (targets_json) {
-      const kjson::Node doc = kjson::parse(targets_json);
-      for (auto& w : doc["workloads"].items) tgUsage.push_back(FlavorSnapshot::parse_usage(w));
-      for (auto& e : doc["targets"].items) {
-        if (e.items.size() != 2) throw std::runtime_error("admit: targets entry is not [id, [workloads]]");
-        std::vector<int32_t> l;
-        for (auto& t : e.items[1].items) l.push_back(int32_t(t.i64()));
-        tgLists.push_back({int32_t(e.items[0].i64()), std::move(l)});
-      }
-      // a column for every resource the targets' usage names (the next upload reloads then)
-      for (auto& us : tgUsage) h->snap->ensure_columns_for_usage(us);
-    }
+    if (tg) check_host_targets(*h->snap, *tg);
     // workloads in ascending id (the gathered quads of every rank; a
     // workload's quads are contiguous per rank), capacity checked first:
     // nothing is admitted when the caller's buffer is short
@@ -5205,44 +5240,28 @@ static int host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, const 
     const auto pods = s.colByName.find("pods");
     const int32_t pods_col = pods == s.colByName.end() ? -1 : pods->second;
     const double t1 = now_ms();
-    if (targets_json) {
-      // RemoveUsage's records per target, as update_usage forms them
-      // (single x count per resource and pods:count, in resource-name order;
-      // a domain that is no leaf of the snapshot is skipped)
-      std::vector<kueue_tas_delta> td;
-      std::vector<int64_t> toff{0};
-      for (auto& us : tgUsage) {
-        for (auto& u : us) {
-          const int32_t leaf = s.leafById.find(u.id);
-          if (leaf < 0) continue;
-          Requests tot;
-          for (auto& kv : u.single) tot[kv.first] = mul64(kv.second, u.count);
-          tot["pods"] = add64(tot["pods"], u.count);
-          for (auto& kv : tot) {
-            const auto col = s.colByName.find(kv.first);
-            if (col == s.colByName.end()) throw std::runtime_error("admit: target resource without a column");
-            td.push_back({leaf, col->second, kv.second});
-          }
-        }
-        toff.push_back(int64_t(td.size()));
-      }
+    if (tg) {
       std::vector<int32_t> pos(W, -1);  // id -> position in the ascending list
       for (size_t k = 0; k < ids.size(); k++) pos[size_t(ids[k])] = int32_t(k);
-      std::vector<const std::vector<int32_t>*> per(ids.size(), nullptr);
-      for (auto& e : tgLists) {
-        if (e.first < 0 || size_t(e.first) >= W || pos[size_t(e.first)] < 0)
+      std::vector<int64_t> per(ids.size(), -1);  // position -> entry
+      for (size_t e = 0; e < tg->E; e++) {
+        const int32_t g = tg->entry_ids[e];
+        if (g < 0 || size_t(g) >= W || pos[size_t(g)] < 0)
           throw std::runtime_error("admit: targets for an entry that is not in the batch");
-        if (per[size_t(pos[size_t(e.first)])]) throw std::runtime_error("admit: targets given twice for one entry");
-        per[size_t(pos[size_t(e.first)])] = &e.second;
+        if (per[size_t(pos[size_t(g)])] >= 0) throw std::runtime_error("admit: targets given twice for one entry");
+        per[size_t(pos[size_t(g)])] = int64_t(e);
       }
       std::vector<int32_t> etg;
       std::vector<int64_t> eoff{0};
       for (size_t k = 0; k < ids.size(); k++) {
-        if (per[k]) etg.insert(etg.end(), per[k]->begin(), per[k]->end());
+        if (per[k] >= 0)
+          etg.insert(etg.end(), tg->entry_targets + tg->entry_off[per[k]], tg->entry_targets + tg->entry_off[per[k] + 1]);
         eoff.push_back(int64_t(etg.size()));
       }
+      const int64_t no_off[1] = {0};
       rc = kueue_tas_admit_targets(s.ctx, fr.data(), fr.size(), terms.data(), terms.size(), off.data(), ids.size(),
-                                   pods_col, td.data(), toff.data(), tgUsage.size(), etg.data(), eoff.data(), adm.data());
+                                   pods_col, tg->deltas, tg->T ? tg->off : no_off, tg->T, etg.data(), eoff.data(),
+                                   adm.data());
     } else {
       rc = kueue_tas_admit(s.ctx, fr.data(), fr.size(), terms.data(), terms.size(), off.data(), ids.size(), pods_col,
                            adm.data());
@@ -5288,12 +5307,67 @@ int kueue_tas_host_admit(kueue_tas_host* h, const int32_t* recs, size_t len, int
 int kueue_tas_host_admit_targets(kueue_tas_host* h, const int32_t* quads, size_t len, const char* targets_json,
                                  int32_t* admitted, size_t admitted_cap, size_t* n_workloads, size_t* n_deltas) {
   if (!targets_json) return KUEUE_TAS_EINVAL;
-  return host_admit(h, quads, len, targets_json, admitted, admitted_cap, n_workloads, n_deltas);
+  if (!h || !h->snap || !h->err.empty()) return KUEUE_TAS_EINVAL;
+  // the JSON form into the binary one: the usage records become delta records
+  // against the uploaded snapshot's leaves and columns
+  std::vector<kueue_tas_delta> td;
+  std::vector<int64_t> toff{0}, eoff{0};
+  std::vector<int32_t> eids, etg;
+  try {
+    const kjson::Node doc = kjson::parse(targets_json);
+    std::vector<std::vector<FlavorSnapshot::DomainUsage>> tgUsage;  // per preemptable workload
+    for (auto& w : doc["workloads"].items) tgUsage.push_back(FlavorSnapshot::parse_usage(w));
+    for (auto& e : doc["targets"].items) {
+      if (e.items.size() != 2) throw std::runtime_error("admit: targets entry is not [id, [workloads]]");
+      eids.push_back(int32_t(e.items[0].i64()));
+      for (auto& t : e.items[1].items) etg.push_back(int32_t(t.i64()));
+      eoff.push_back(int64_t(etg.size()));
+    }
+    // a column for every resource the targets' usage names (the upload reloads then)
+    for (auto& us : tgUsage) h->snap->ensure_columns_for_usage(us);
+    const int rc = h->snap->upload();
+    if (rc) {
+      h->err = h->snap->err;
+      return rc;
+    }
+    for (auto& us : tgUsage) {
+      usage_to_deltas(*h->snap, us, td);
+      toff.push_back(int64_t(td.size()));
+    }
+  } catch (const std::exception& e) {
+    h->err = e.what();
+    return KUEUE_TAS_EINVAL;
+  }
+  const HostAdmitTargets tg{td.data(), toff.data(), toff.size() - 1, eids.data(), eoff.data(), etg.data(), eids.size()};
+  return host_admit(h, quads, len, &tg, admitted, admitted_cap, n_workloads, n_deltas);
 }
 
-int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t row_words, const int64_t* lens,
-                               int32_t world, int32_t* admitted, size_t admitted_cap, size_t* n_workloads,
-                               size_t* n_deltas) {
+int kueue_tas_host_usage_deltas(kueue_tas_host* h, const char* usage_json, kueue_tas_delta* buf, size_t cap,
+                                size_t* len) {
+  if (!h || !h->snap || !h->err.empty() || !usage_json || !len || (cap && !buf)) return KUEUE_TAS_EINVAL;
+  try {
+    const auto us = FlavorSnapshot::parse_usage(kjson::parse(usage_json));
+    h->snap->ensure_columns_for_usage(us);
+    const int rc = h->snap->upload();
+    if (rc) {
+      h->err = h->snap->err;
+      return rc;
+    }
+    std::vector<kueue_tas_delta> td;
+    usage_to_deltas(*h->snap, us, td);
+    *len = td.size();
+    if (cap < td.size()) return KUEUE_TAS_EOVERFLOW;
+    std::copy(td.begin(), td.end(), buf);
+    return 0;
+  } catch (const std::exception& e) {
+    h->err = e.what();
+    return KUEUE_TAS_EINVAL;
+  }
+}
+
+static int host_admit_block(kueue_tas_host* h, const int32_t* block, size_t row_words, const int64_t* lens,
+                            int32_t world, const HostAdmitTargets* tg, int32_t* admitted, size_t admitted_cap,
+                            size_t* n_workloads, size_t* n_deltas) {
   if (!h || !h->snap || !h->err.empty() || !block || !lens || world < 1 || !n_workloads) return KUEUE_TAS_EINVAL;
   try {
     FlavorSnapshot& s = *h->snap;
@@ -5303,6 +5377,7 @@ int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t r
       h->err = s.err;
       return rc;
     }
+    if (tg) check_host_targets(s, *tg);
     const size_t W = h->compiled.size();
     // the compiled workloads' per-PodSet request terms on the device, rebuilt
     // when the compiled set or the columns change
@@ -5334,7 +5409,12 @@ int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t r
     const kueue_tas_delta* dl = nullptr;
     size_t nw = 0, nd = 0;
     const double t1 = now_ms();
-    rc = kueue_tas_admit_block(s.ctx, block, row_words, lens, world, pods_col, ids.data(), adm.data(), W, &nw, &dl, &nd);
+    if (tg)
+      rc = kueue_tas_admit_block_targets(s.ctx, block, row_words, lens, world, pods_col, tg->deltas, tg->off, tg->T,
+                                         tg->entry_ids, tg->entry_off, tg->entry_targets, tg->E, ids.data(), adm.data(),
+                                         W, &nw, &dl, &nd);
+    else
+      rc = kueue_tas_admit_block(s.ctx, block, row_words, lens, world, pods_col, ids.data(), adm.data(), W, &nw, &dl, &nd);
     if (rc == KUEUE_TAS_ELAYOUT || rc == KUEUE_TAS_EHOSTMEM) {  // the quads through the host path
       std::vector<int32_t> quads;
       for (int32_t r = 0; r < world; r++) {
@@ -5347,12 +5427,15 @@ int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t r
           throw std::runtime_error("admit: block copy");
         }
       }
-      return kueue_tas_host_admit(h, quads.data(), quads.size(), admitted, admitted_cap, n_workloads, n_deltas);
+      const int hrc = host_admit(h, quads.data(), quads.size(), tg, admitted, admitted_cap, n_workloads, n_deltas);
+      if (hrc == 0 || hrc == KUEUE_TAS_EOVERFLOW) h->admit_block_path = 0;
+      return hrc;
     }
-    if (rc && rc != KUEUE_TAS_EOVERFLOW) {
+    if (rc && rc != KUEUE_TAS_EOVERFLOW) {  // (nothing admitted: the path flag stays the last admission's)
       h->err = std::string("admit: ") + kueue_tas_last_error(s.ctx);
       return rc;
     }
+    h->admit_block_path = 1;
     *n_workloads = nw;
     if (rc == KUEUE_TAS_EOVERFLOW || !admitted || admitted_cap < 2 * nw) return KUEUE_TAS_EOVERFLOW;
     const double t2 = now_ms();
@@ -5372,6 +5455,25 @@ int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t r
     return KUEUE_TAS_EINVAL;
   }
 }
+
+int kueue_tas_host_admit_block(kueue_tas_host* h, const int32_t* block, size_t row_words, const int64_t* lens,
+                               int32_t world, int32_t* admitted, size_t admitted_cap, size_t* n_workloads,
+                               size_t* n_deltas) {
+  return host_admit_block(h, block, row_words, lens, world, nullptr, admitted, admitted_cap, n_workloads, n_deltas);
+}
+
+int kueue_tas_host_admit_block_targets(kueue_tas_host* h, const int32_t* block, size_t row_words, const int64_t* lens,
+                                       int32_t world, const kueue_tas_delta* target_deltas, const int64_t* target_off,
+                                       size_t n_targets, const int32_t* entry_ids, const int64_t* entry_target_off,
+                                       const int32_t* entry_targets, size_t n_entries, int32_t* admitted,
+                                       size_t admitted_cap, size_t* n_workloads, size_t* n_deltas) {
+  const HostAdmitTargets tg{target_deltas, target_off, n_targets, entry_ids, entry_target_off, entry_targets, n_entries};
+  return host_admit_block(h, block, row_words, lens, world, &tg, admitted, admitted_cap, n_workloads, n_deltas);
+}
+
+int kueue_tas_host_last_admit_block_path(kueue_tas_host* h) { return h ? h->admit_block_path : -1; }
+
+uint64_t kueue_tas_host_column_generation(kueue_tas_host* h) { return h && h->snap ? h->snap->col_gen : 0; }
 
 int kueue_tas_host_last_admit_stats(kueue_tas_host* h, int64_t* out3) {
   if (!h || !h->snap || !h->snap->ctx || !out3) return KUEUE_TAS_EINVAL;

@@ -6940,7 +6940,7 @@ __device__ __forceinline__ int admit_delta_count(const kueue_tas_fits_req* reqs,
                                                  const int32_t* admitted, int n, int pods_col, int i) {
   if (i >= n) return 0;
   const kueue_tas_fits_req r = reqs[i];
-  if (!admitted[rec_wl[i]] || r.leaf < 0) return 0;
+  if (admitted[rec_wl[i]] != 1 || r.leaf < 0) return 0;  // (2: skipped for overlapping targets, its usage not added)
   return r.num_terms + (pods_col >= 0 ? 1 : 0);
 }
 __global__ __launch_bounds__(256) void admit_delta_blocks_kernel(const kueue_tas_fits_req* reqs, const int32_t* rec_wl,
@@ -6996,6 +6996,89 @@ __global__ __launch_bounds__(256) void admit_delta_write_kernel(const kueue_tas_
     out[o++] = kueue_tas_delta{r.leaf, t.col, int64_t(uint64_t(t.value) * uint64_t(int64_t(r.count)))};
   }
   if (pods_col >= 0) out[o] = kueue_tas_delta{r.leaf, pods_col, int64_t(r.count)};
+}
+
+// ---- the gathered block with preemption targets (kueue_tas_admit_block_targets) ----
+// The entries' target lists arrive keyed by workload id (the caller cannot
+// know a workload's position before the call: admit_block_offsets_kernel
+// derives the ascending order here).  One workgroup turns them into what
+// admit_step_kernel and the host's run segmentation take by position:
+//  1. a thread per entry finds its id in the ascending ids (binary search)
+//     and claims the position (ent_of[k] = entry + 1, zero on entry): an id
+//     without a header in the block, or a position claimed twice, is an error
+//     bit (AdmitEntryErr);
+//  2. a scan over the positions (as admit_block_offsets_kernel's) lays the
+//     lists out in position order: eoff[n_wl + 1], etg; `has` gets one bit per
+//     position that carries targets (the wave's ballot, whole words per wave).
+enum AdmitEntryErr { AEE_ABSENT = 1, AEE_DUP = 2 };
+__global__ __launch_bounds__(1024) void admit_block_entries_kernel(const int32_t* hdr, const int32_t* ids,
+                                                                   const int32_t* entry_ids, const int64_t* entry_off,
+                                                                   const int32_t* entry_targets, int n_entries,
+                                                                   int32_t* ent_of, int64_t* eoff, int32_t* etg,
+                                                                   uint32_t* has, int32_t* err) {
+  __shared__ int32_t sh_c[16];
+  const int lane = lane_id(), wave = int(threadIdx.x) >> 6, nw = int(blockDim.x) >> 6;
+  const int n_wl = hdr[0];
+  int32_t bad = 0;
+  for (int e = int(threadIdx.x); e < n_entries; e += int(blockDim.x)) {
+    const int32_t g = entry_ids[e];
+    int lo = 0, hi = n_wl;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ids[mid] < g) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo >= n_wl || ids[lo] != g) bad |= AEE_ABSENT;
+    else if (atomicMax(ent_of + lo, e + 1) != 0) bad |= AEE_DUP;
+  }
+  if (bad) atomicOr(err, bad);
+  __syncthreads();
+  int64_t base = 0;
+  for (int c0 = 0; c0 < n_wl; c0 += int(blockDim.x)) {  // block-uniform
+    const int k = c0 + int(threadIdx.x);
+    const int32_t e = k < n_wl ? load_l2_i32(ent_of + k) - 1 : -1;  // (claimed by atomics: read at L2)
+    const int64_t s0 = e >= 0 ? entry_off[e] : 0;
+    const int32_t len = e >= 0 ? int32_t(entry_off[e + 1] - s0) : 0;
+    int tc;
+    const int ex = wave_excl_scan(len, &tc);
+    const uint64_t m = ballot(len > 0);
+    if (lane == 0) {
+      sh_c[wave] = tc;
+      has[(c0 >> 5) + 2 * wave] = uint32_t(m);
+      has[(c0 >> 5) + 2 * wave + 1] = uint32_t(m >> 32);
+    }
+    __syncthreads();
+    int64_t o = base;
+    int32_t tot = 0;
+    for (int q = 0; q < nw; q++) {
+      if (q < wave) o += sh_c[q];
+      tot += sh_c[q];
+    }
+    if (k < n_wl) {
+      eoff[k] = o + ex;
+      for (int32_t i = 0; i < len; i++) etg[o + ex + i] = entry_targets[s0 + i];
+    }
+    base += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) eoff[n_wl] = base;
+}
+
+// The pass (admit_run_view) takes record -> workload and the workload offsets
+// relative to its run; admit_block_records_kernel wrote rec_wl absolute (the
+// delta kernels index the verdicts by it).  Per pass run q = (a, b, at) of
+// `bounds` (workload positions [a, b), its offsets at roff[at ..]):
+// roff[at + w - a] = wl_off[w] - wl_off[a] and, for the run's records,
+// rel_wl[i] = rec_wl[i] - a.  Blocks (x, q) stride over the run.
+__global__ __launch_bounds__(256) void admit_block_runs_kernel(const int64_t* bounds, int n_runs, const int64_t* wl_off,
+                                                               const int32_t* rec_wl, int64_t* roff, int32_t* rel_wl) {
+  const int64_t stride = int64_t(gridDim.x) * blockDim.x, t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  for (int q = int(blockIdx.y); q < n_runs; q += int(gridDim.y)) {
+    const int64_t a = bounds[3 * q], b = bounds[3 * q + 1], at = bounds[3 * q + 2];
+    const int64_t r0 = wl_off[a], r1 = wl_off[b];
+    for (int64_t w = a + t; w <= b; w += stride) roff[at + (w - a)] = wl_off[w] - r0;
+    for (int64_t i = r0 + t; i < r1; i += stride) rel_wl[i] = rec_wl[i] - int32_t(a);
+  }
 }
 
 }  // namespace ktas

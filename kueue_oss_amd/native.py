@@ -72,7 +72,8 @@ EXPORTED_SYMBOLS = [
     "kueue_tas_select_groups", "kueue_tas_admit_table", "kueue_tas_admit_block", "kueue_tas_copy_to_host",
     "kueue_tas_host_admit_block", "kueue_tas_admit_targets", "kueue_tas_host_admit_targets",
     "kueue_tas_last_admit_launches", "kueue_tas_host_last_admit_launches", "kueue_tas_host_last_counters",
-    "kueue_tas_eval_generation",
+    "kueue_tas_eval_generation", "kueue_tas_admit_block_targets", "kueue_tas_host_admit_block_targets",
+    "kueue_tas_host_usage_deltas", "kueue_tas_host_last_admit_block_path", "kueue_tas_host_column_generation",
 ]
 
 # the Makefile's SRC_HASH inputs, in order
@@ -236,6 +237,18 @@ def _bind(lib):
     lib.kueue_tas_last_counters.restype = c.c_int
     lib.kueue_tas_last_fill_paths.argtypes = [c.c_void_p]
     lib.kueue_tas_last_fill_paths.restype = c.c_uint32
+    # (bound last: tools load builds of earlier commits, which lack them, through this function)
+    lib.kueue_tas_host_admit_block_targets.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_int32,
+                                                       c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p,
+                                                       c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t,
+                                                       c.POINTER(c.c_size_t), c.POINTER(c.c_size_t)]
+    lib.kueue_tas_host_admit_block_targets.restype = c.c_int
+    lib.kueue_tas_host_usage_deltas.argtypes = [c.c_void_p, c.c_char_p, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    lib.kueue_tas_host_usage_deltas.restype = c.c_int
+    lib.kueue_tas_host_last_admit_block_path.argtypes = [c.c_void_p]
+    lib.kueue_tas_host_last_admit_block_path.restype = c.c_int
+    lib.kueue_tas_host_column_generation.argtypes = [c.c_void_p]
+    lib.kueue_tas_host_column_generation.restype = c.c_uint64
 
 
 def resource_quantity_string(name: str, value: int, lib=None) -> str:
@@ -609,12 +622,77 @@ class TASFlavorSnapshot:
             raise RuntimeError(self._err())
         return tuple(out)
 
-    def admit_block(self, block, lens, row_words=None):
+    def usage_deltas(self, records: list):
+        """The delta records (numpy DELTA_DTYPE) of a workload's usage records, as
+        admit_with_targets forms them for a target (kueue_tas_host_usage_deltas):
+        what admit_block takes as a preemptable workload.  They name the
+        snapshot's columns: build them after the cycle's compile(); a resource
+        that gets a column later (kueue_tas_host_column_generation moves)
+        renumbers the columns, and the arrays are to be rebuilt."""
+        import numpy as np
+        doc = json.dumps(records).encode()
+        n = ctypes.c_size_t()
+        rc = self._lib.kueue_tas_host_usage_deltas(self._h, doc, None, 0, ctypes.byref(n))
+        if rc not in (0, -5):
+            raise RuntimeError(self._err())
+        out = np.zeros(n.value, dtype=DELTA_DTYPE)
+        if n.value and self._lib.kueue_tas_host_usage_deltas(self._h, doc, out.ctypes.data, out.size, ctypes.byref(n)):
+            raise RuntimeError(self._err())
+        return out
+
+    def _target_table(self, workloads):
+        """(records, offsets) of the preemptable workloads: DELTA_DTYPE arrays as
+        they are, usage-record lists through usage_deltas."""
+        import numpy as np
+        lists = [w for w in workloads if not isinstance(w, np.ndarray)]
+        gen0 = self._lib.kueue_tas_host_column_generation(self._h)
+        if lists:  # every resource a column before the first conversion (a new column renumbers them)
+            self.usage_deltas([r for w in lists for r in w])
+        gen = self._lib.kueue_tas_host_column_generation(self._h)
+        if lists and len(lists) < len(workloads) and gen != gen0:
+            # the lists named a resource without a column: the arrays' column indices are of the old set
+            raise RuntimeError("admit_block: the usage-record lists added a resource column; the delta arrays "
+                               "given beside them name the columns from before (rebuild them with usage_deltas)")
+        parts = [np.ascontiguousarray(w, dtype=DELTA_DTYPE) if isinstance(w, np.ndarray) else self.usage_deltas(w)
+                 for w in workloads]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        np.cumsum([len(p) for p in parts], out=off[1:])
+        flat = np.concatenate(parts) if parts else np.zeros(0, dtype=DELTA_DTYPE)
+        return np.ascontiguousarray(flat, dtype=DELTA_DTYPE), off
+
+    def last_admit_block_path(self):
+        """Where the last admit_block admitted: "device" (from the block), "host"
+        (the fallback: a block outside the assignments layout or in host
+        memory), None before the first call."""
+        return {1: "device", 0: "host"}.get(self._lib.kueue_tas_host_last_admit_block_path(self._h))
+
+    def admit_block(self, block, lens, row_words=None, workloads=None, targets=None):
         """admit() from the all-gather's receive block on the device
         (kueue_tas_host_admit_block): ``block`` a [world, row_words] int32
         tensor (rows [len, quads...]) or a raw device pointer with
-        ``row_words``, ``lens`` the rows' lengths.  Same return value."""
+        ``row_words``, ``lens`` the rows' lengths.  Same return value.
+        With ``workloads`` (the preemptable workloads, each a DELTA_DTYPE
+        array — its admission's deltas, or usage_deltas() — or a usage-record
+        list) and ``targets`` as in admit_with_targets: that call from the
+        block (kueue_tas_host_admit_block_targets), verdicts 0 / 1 / 2."""
         import numpy as np
+        items = list(targets.items() if hasattr(targets, "items") else (targets or []))
+        if items:  # (no entry named: the plain call, as without the arguments)
+            td, toff = self._target_table(workloads or [])
+            eids = np.array([int(i) for i, _ in items], dtype=np.int32)
+            eoff = np.zeros(len(items) + 1, dtype=np.int64)
+            np.cumsum([len(ts) for _, ts in items], out=eoff[1:])
+            etg = np.array([int(t) for _, ts in items for t in ts], dtype=np.int32)
+
+            def call(ptr, row_words, ln, adm, nw, nd):
+                return self._lib.kueue_tas_host_admit_block_targets(
+                    self._h, ptr, row_words, ln.ctypes.data, ln.size, td.ctypes.data, toff.ctypes.data, len(toff) - 1,
+                    eids.ctypes.data, eoff.ctypes.data, etg.ctypes.data, eids.size, adm.ctypes.data, adm.size,
+                    ctypes.byref(nw), ctypes.byref(nd))
+        else:
+            def call(ptr, row_words, ln, adm, nw, nd):
+                return self._lib.kueue_tas_host_admit_block(self._h, ptr, row_words, ln.ctypes.data, ln.size,
+                                                            adm.ctypes.data, adm.size, ctypes.byref(nw), ctypes.byref(nd))
         if hasattr(block, "data_ptr"):
             ptr, row_words = block.data_ptr(), int(block.shape[1])
         elif hasattr(block, "ctypes"):  # a host array (the CPU emulator's device memory)
@@ -627,8 +705,7 @@ class TASFlavorSnapshot:
             adm = np.zeros((cap, 2), dtype=np.int32)
             nw = ctypes.c_size_t()
             nd = ctypes.c_size_t()
-            rc = self._lib.kueue_tas_host_admit_block(self._h, ptr, row_words, ln.ctypes.data, ln.size,
-                                                      adm.ctypes.data, adm.size, ctypes.byref(nw), ctypes.byref(nd))
+            rc = call(ptr, row_words, ln, adm, nw, nd)
             if rc == -5 and nw.value > cap:
                 cap = nw.value
                 continue

@@ -159,14 +159,34 @@ def broadcast_deltas(deltas, dist, src: int = 0, device=None):
         _grow("deltas", k)
 
 
-def admit_round(snap, world: int, rank: int, dist, device=None, src: int = 0):
+def admit_round(snap, world: int, rank: int, dist, device=None, src: int = 0, workloads=None, targets=None):
     """One nominate/admit round after every rank's run_compiled: all-gather the
     assignments, rank ``src`` admits in workload order (Fits + AddUsage on its
     replica) and broadcasts the applied deltas, the other replicas apply them.
     Returns (gathered quads, admitted (id, 0/1) pairs or None off-src, deltas).
     Over RCCL the gathered block stays on the device: rank ``src`` admits
     from it (kueue_tas_host_admit_block: records and deltas built on the
-    device, no host round trip of the quads) and the quads returned are None."""
+    device, no host round trip of the quads) and the quads returned are None.
+    ``workloads`` / ``targets`` (read on rank ``src`` only): the cycle's
+    entries carry preemption targets, as in admit_with_targets — from the
+    block over RCCL (admit_block with targets), admit_with_targets over the
+    gathered quads otherwise; the pairs then hold verdicts 0 / 1 / 2."""
+    with_targets = workloads is not None or targets is not None
+
+    def admit(quads, block, lens):
+        if not with_targets:
+            return snap.admit(quads) if block is None else snap.admit_block(block, lens)
+        if block is None:
+            import numpy as np
+
+            if not any(isinstance(w, np.ndarray) for w in workloads or []):
+                return snap.admit_with_targets(quads, workloads or [], targets or {})
+            # delta arrays have no JSON form: the quads as a one-row host block (admitted through the host path)
+            q = np.ascontiguousarray(quads, dtype=np.int32).reshape(-1)
+            row = np.concatenate([np.array([q.size], dtype=np.int32), q]).reshape(1, -1)
+            return snap.admit_block(row, [q.size], workloads=workloads, targets=targets or {})
+        return snap.admit_block(block, lens, workloads=workloads or [], targets=targets or {})
+
     quads = block = lens = None
     if device is not None and str(device).startswith("cuda"):
         block, lens = gather_assignments(snap.last_assignments(), world, dist, device, to_host=False)
@@ -176,7 +196,7 @@ def admit_round(snap, world: int, rank: int, dist, device=None, src: int = 0):
     deltas = None
     if rank == src:
         try:
-            admitted, deltas = snap.admit(quads) if block is None else snap.admit_block(block, lens)
+            admitted, deltas = admit(quads, block, lens)
         except Exception:
             # a failed admission must not leave the other ranks waiting in the
             # broadcast: send the failure count (-1) so every rank raises
