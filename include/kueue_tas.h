@@ -444,9 +444,38 @@ int kueue_tas_admit_targets(kueue_tas_ctx* ctx, const kueue_tas_fits_req* reqs, 
  * workloads in ascending id in ids[0 .. *n_workloads), admitted[] their
  * verdicts (cap: KUEUE_TAS_EOVERFLOW when short, nothing admitted), and the
  * applied delta list in kueue_tas_host_admit's order (*deltas valid until the
- * next call).  KUEUE_TAS_ELAYOUT (nothing admitted) when the block is not in
- * that layout or has more than 16 rows, KUEUE_TAS_EHOSTMEM when it is not
- * device memory: the caller admits through the host path. */
+ * next call).
+ * The block's words are another process's: for ANY words the call returns 0,
+ * KUEUE_TAS_ELAYOUT, _EHOSTMEM or _EINVAL and reads only the rows' lens[r]
+ * words; on every error nothing is admitted, the usage is untouched and ids[]
+ * and admitted[] are not written.  In the order checked:
+ *   KUEUE_TAS_EINVAL   a row length that is negative, no multiple of 4 or, with
+ *                      its length word, above row_words; no admission table;
+ *   KUEUE_TAS_EHOSTMEM the block is not device memory (any number of rows);
+ *   KUEUE_TAS_ELAYOUT  more than 16 rows or more than INT32_MAX quads; or the
+ *                      quads are not exactly headers each followed by its own
+ *                      run: a header id outside the table's workloads or given
+ *                      twice (in one row or two), a count n that is negative or
+ *                      leaves the row (compared in 64 bits), rows whose headers'
+ *                      1 + n do not add up to the row's quads (runs that overlap,
+ *                      a run across two rows, a domain quad before, between or
+ *                      behind the runs, with or without a header of its id), a
+ *                      run that holds a header or a quad of another id.  A
+ *                      failed header may have domain quads (checked alike) and
+ *                      a header may have none.
+ *   KUEUE_TAS_EINVAL   in a block of that layout, what kueue_tas_host_admit
+ *                      rejects: a domain quad whose PodSet is not the
+ *                      workload's or whose leaf is outside [0, N); a term used
+ *                      by a record whose column is outside [0, R) of the
+ *                      snapshot loaded NOW (-1: a resource without a column; or
+ *                      a table uploaded before a reload that left fewer columns).
+ * After ELAYOUT and EHOSTMEM the caller admits through the host path
+ * (kueue_tas_host_admit_block does), which gives for the same quads what this
+ * call gives for a block in the layout.
+ * kueue_tas_admit_table returns KUEUE_TAS_EINVAL, keeping the table it had, for
+ * PodSet or term ranges outside the arrays and for a term column below -1 or
+ * not below R of the loaded snapshot (KUEUE_TAS_MAX_COLS before the first
+ * load); -1 is accepted, for the call to report when a record uses the term. */
 /* bytes from device memory of ctx's device to host memory (synchronous) */
 int kueue_tas_copy_to_host(kueue_tas_ctx* ctx, void* dst, const void* src, size_t bytes);
 int kueue_tas_admit_table(kueue_tas_ctx* ctx, const int32_t* ps_base, int32_t num_workloads, const int32_t* ps_terms,

@@ -1661,6 +1661,12 @@ int kueue_tas_admit_table(kueue_tas_ctx* c, const int32_t* ps_base, int32_t num_
   for (int32_t p = 0; p < P; p++)
     if (ps_terms[2 * p] < 0 || ps_terms[2 * p + 1] < 0 || size_t(ps_terms[2 * p]) + size_t(ps_terms[2 * p + 1]) > num_terms)
       return fail(c, KUEUE_TAS_EINVAL, "admit table: term range");
+  // -1 (a resource without a column) is the call's to report, for the terms
+  // its records use, as kueue_tas_host_admit does; so is a column the
+  // snapshot lost in a later reload (admit_block_records_kernel: col >= R)
+  const int32_t col_end = c->loaded ? c->snap.R : KUEUE_TAS_MAX_COLS;
+  for (size_t t = 0; t < num_terms; t++)
+    if (terms[t].col < -1 || terms[t].col >= col_end) return fail(c, KUEUE_TAS_EINVAL, "admit table: term column out of range");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, c->d_adm_ps.ensure(size_t(num_workloads) + 1 + 2 * size_t(P)));
   HIPCHK(c, c->d_adm_terms.ensure(std::max<size_t>(num_terms, 1)));
@@ -1811,7 +1817,6 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
   if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
   if (!block || !lens || !ids || !admitted || !n_workloads || !deltas || !n_deltas || world < 1)
     return fail(c, KUEUE_TAS_EINVAL, "null argument");
-  if (world > kAdmitMaxRows) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: more rows than supported");
   if (c->adm_W < 0) return fail(c, KUEUE_TAS_EINVAL, "admit block: no admission table (kueue_tas_admit_table)");
   if (pods_col < -1 || pods_col >= c->snap.R) return fail(c, KUEUE_TAS_EINVAL, "pods column out of range");
   if (bt) {
@@ -1826,11 +1831,9 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
   rows.world = world;
   size_t Q = 0;
   int32_t maxq = 0;
-  for (int r = 0; r < world; r++) {
+  for (int r = 0; r < world; r++) {  // every row's, also of a block the fallback reads (EHOSTMEM, more rows than supported)
     if (lens[r] < 0 || lens[r] % 4 || size_t(lens[r]) + 1 > row_words) return fail(c, KUEUE_TAS_EINVAL, "admit block: row length");
-    rows.nq[r] = int32_t(lens[r] / 4);
-    maxq = std::max(maxq, rows.nq[r]);
-    Q += size_t(rows.nq[r]);
+    Q += size_t(lens[r] / 4);
   }
   const int W = c->adm_W;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1840,6 +1843,13 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
       (void)hipGetLastError();
       return fail(c, KUEUE_TAS_EHOSTMEM, "admit block: not device memory");
     }
+  }
+  // (after the pointer's type: the fallback copies a device block and reads a host block)
+  if (world > kAdmitMaxRows) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: more rows than supported");
+  if (Q > size_t(INT32_MAX)) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: more quads than supported");
+  for (int r = 0; r < world; r++) {
+    rows.nq[r] = int32_t(lens[r] / 4);
+    maxq = std::max(maxq, rows.nq[r]);
   }
   // the layout of the host path with the bounds (records <= quads, workloads <= W)
   const AdmitLayout L = admit_layout(std::max<size_t>(Q, 1), 0, size_t(W), size_t(c->snap.N));
@@ -1867,6 +1877,9 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
   uint8_t* d = c->d_fits.p;
   int32_t* hdr = reinterpret_cast<int32_t*>(d + o_hdr);  // [0] workloads [1] records [2] deltas [3] errors [4] negative
                                                          // [5] entry errors (AdmitEntryErr)
+  // behind them, per row: the sum of 1 + n over its headers (admit_block_headers_kernel)
+  constexpr size_t kRowSumAt = 64, kHdrD2H = kRowSumAt + kAdmitMaxRows * 8;
+  static_assert(kHdrD2H <= 256, "the header words and the row sums share the zeroed 256 bytes");
   // pinned host words: the plain call's, then the bitmap, the workload offsets (int64) and, for ids given
   // with empty lists only, the headers' flags
   const size_t a_has = (size_t(W) + 3 + 64 + KUEUE_TAS_MAX_COLS * 4 + 1) / 2 * 2, a_off = a_has + hwords,
@@ -1891,7 +1904,8 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
   if (maxq > 0) {
     hipLaunchKernelGGL(admit_block_headers_kernel, dim3(unsigned((maxq + 255) / 256), unsigned(world)), dim3(256), 0,
                        c->stream, block, rows, W, reinterpret_cast<int32_t*>(d + o_flag),
-                       reinterpret_cast<int64_t*>(d + o_pos), reinterpret_cast<int32_t*>(d + o_nd), hdr + 3);
+                       reinterpret_cast<int64_t*>(d + o_pos), reinterpret_cast<int32_t*>(d + o_nd),
+                       reinterpret_cast<unsigned long long*>(d + o_hdr + kRowSumAt), hdr + 3);
     HIPCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(admit_block_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, W,
@@ -1910,10 +1924,18 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
     HIPCHK(c, hipMemcpyAsync(hh + a_has, d + x_has, hwords * 4, hipMemcpyDeviceToHost, c->stream));
   }
   if (chk) HIPCHK(c, hipMemcpyAsync(hh + a_flag, d + o_flag, size_t(W) * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(hh, hdr, tgt ? 32 : 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hh, hdr, kHdrD2H, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int32_t n_wl = hh[0], n = hh[1];
-  if (hh[3] & (ABE_DUP | ABE_LAYOUT | ABE_ID)) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: not the assignments layout");
+  // every row tiled by its headers' runs (with no header twice and, below,
+  // every run quad its workload's: no overlap, no quad outside a run), so
+  // the records are at most the quads the layout was sized for
+  bool tiled = n >= 0 && size_t(n) <= Q;
+  uint64_t row_sum[kAdmitMaxRows];
+  memcpy(row_sum, reinterpret_cast<const uint8_t*>(hh) + kRowSumAt, sizeof row_sum);
+  for (int r = 0; r < world; r++) tiled = tiled && row_sum[r] == uint64_t(rows.nq[r]);
+  if ((hh[3] & (ABE_DUP | ABE_LAYOUT | ABE_ID)) || !tiled)
+    return fail(c, KUEUE_TAS_ELAYOUT, "admit block: not the assignments layout");
   if (tgt && (hh[5] & AEE_ABSENT)) return fail(c, KUEUE_TAS_EINVAL, "entry id without a header in the block");
   if (tgt && (hh[5] & AEE_DUP)) return fail(c, KUEUE_TAS_EINVAL, "entry id given twice");
   if (chk)
@@ -1949,7 +1971,7 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
                        c->snap.N, W, reinterpret_cast<const int32_t*>(d + o_ids), reinterpret_cast<const int64_t*>(d + L.o_off),
                        reinterpret_cast<const int32_t*>(d + o_flag), reinterpret_cast<const int64_t*>(d + o_pos),
                        reinterpret_cast<const int32_t*>(d + o_nd), c->d_adm_ps.p, c->d_adm_ps.p + W + 1,
-                       c->d_adm_terms.p, n_wl, pods_col, reinterpret_cast<kueue_tas_fits_req*>(d),
+                       c->d_adm_terms.p, n_wl, pods_col, c->snap.R, reinterpret_cast<kueue_tas_fits_req*>(d),
                        reinterpret_cast<int32_t*>(d + L.o_recwl), reinterpret_cast<unsigned long long*>(d + o_tot),
                        hdr + 4, hdr + 3);
     HIPCHK(c, hipGetLastError());
@@ -1961,8 +1983,8 @@ static int admit_block_impl(kueue_tas_ctx* c, const int32_t* block, size_t row_w
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const int32_t errs = hh[3];
   if (errs & ABE_LAYOUT) return fail(c, KUEUE_TAS_ELAYOUT, "admit block: not the assignments layout");
-  if (errs & ABE_RANGE) return fail(c, KUEUE_TAS_EINVAL, "admit: record out of range");
-  if (errs & ABE_COL) return fail(c, KUEUE_TAS_EINVAL, "admit: request resource without a column");
+  if (errs & ABE_RANGE) return fail(c, KUEUE_TAS_EINVAL, "record out of range");
+  if (errs & ABE_COL) return fail(c, KUEUE_TAS_EINVAL, "request resource without a column");
   bool exact = hh[4] != 0;
   const uint64_t* tot = reinterpret_cast<const uint64_t*>(hh + 8);
   int64_t tot64[KUEUE_TAS_MAX_COLS];

@@ -6786,9 +6786,15 @@ enum AdmitBlockErr { ABE_ID = 1, ABE_RANGE = 2, ABE_DUP = 4, ABE_LAYOUT = 8, ABE
 
 // One thread per quad slot of every row: a header records its workload's
 // run (the row position of its first domain quad, the quad count, failed).
+// A count that is negative or leaves the row (compared in int64: q + 1 + n
+// wraps in 32 bits) is stored as 0, so nothing scans or walks it, and sets
+// ABE_LAYOUT.  row_sum[r] takes 1 + n per header: the runs tile the row
+// exactly when it ends at nq[r], no header is given twice and every quad of
+// a run is a domain quad of its workload (admit_block_records_kernel) — two
+// runs cannot overlap without one holding the other's header.
 __global__ __launch_bounds__(256) void admit_block_headers_kernel(const int32_t* block, AdmitRows rows, int W,
                                                                   int32_t* wl_flag, int64_t* wl_pos, int32_t* wl_nd,
-                                                                  int32_t* err) {
+                                                                  unsigned long long* row_sum, int32_t* err) {
   const int r = int(blockIdx.y);
   const int q = int(blockIdx.x * blockDim.x + threadIdx.x);
   if (r >= rows.world || q >= rows.nq[r]) return;
@@ -6800,9 +6806,11 @@ __global__ __launch_bounds__(256) void admit_block_headers_kernel(const int32_t*
     return;
   }
   if (atomicAdd(wl_flag + g, p[2] != 0 ? 2 : 1) != 0) atomicOr(err, ABE_DUP);  // one header per workload
+  const bool in_row = p[3] >= 0 && int64_t(q) + 1 + int64_t(p[3]) <= int64_t(rows.nq[r]);
   wl_pos[g] = int64_t(r) * rows.row_words + 1 + 4 * (int64_t(q) + 1);
-  wl_nd[g] = p[3];
-  if (p[3] < 0 || q + 1 + p[3] > rows.nq[r]) atomicOr(err, ABE_LAYOUT);
+  wl_nd[g] = in_row ? p[3] : 0;
+  if (!in_row) atomicOr(err, ABE_LAYOUT);
+  else atomicAdd(row_sum + r, (unsigned long long)(1 + p[3]));
 }
 
 // One workgroup: the present workloads in id order (ids, fit0 = 1) and their
@@ -6862,7 +6870,7 @@ __global__ __launch_bounds__(1024) void admit_block_offsets_kernel(int W, const 
 __global__ __launch_bounds__(256) void admit_block_records_kernel(
     const int32_t* block, int N, int W, const int32_t* ids, const int64_t* wl_off, const int32_t* wl_flag,
     const int64_t* wl_pos, const int32_t* wl_nd, const int32_t* ps_base, const int32_t* ps_terms,
-    const kueue_tas_fits_term* terms, int n_wl, int pods_col, kueue_tas_fits_req* reqs, int32_t* rec_wl,
+    const kueue_tas_fits_term* terms, int n_wl, int pods_col, int R, kueue_tas_fits_req* reqs, int32_t* rec_wl,
     unsigned long long* tot, int32_t* ex, int32_t* err) {
   // the block's per-column totals in LDS first (one global atomic per column
   // and block: device-scope atomics on a handful of addresses from every
@@ -6881,15 +6889,20 @@ __global__ __launch_bounds__(256) void admit_block_records_kernel(
   if (k < n_wl) {
     const int32_t g = ids[k];
     const int64_t base = wl_off[k];
-    if (wl_flag[g] >= 2) {  // a failed evaluation is never admitted
+    const int32_t nd = wl_nd[g];
+    const int64_t pos = wl_pos[g];
+    const int32_t ps0 = ps_base[g], nps = ps_base[g + 1] - ps0;
+    if (wl_flag[g] >= 2) {  // a failed evaluation is never admitted; its quads are checked as the host path's
       if (lane == 0) {
         reqs[base] = kueue_tas_fits_req{-1, 0, 0, 0};
         rec_wl[base] = k;
       }
+      for (int j = lane; j < nd; j += kWave) {
+        const int32_t* p = block + pos + 4 * int64_t(j);
+        if (p[0] != g || p[1] < 0) bad |= ABE_LAYOUT;
+        else if (p[1] >= nps || p[2] < 0 || p[2] >= N) bad |= ABE_RANGE;
+      }
     } else {
-      const int32_t nd = wl_nd[g];
-      const int64_t pos = wl_pos[g];
-      const int32_t ps0 = ps_base[g], nps = ps_base[g + 1] - ps0;
       for (int j = lane; j < nd; j += kWave) {
         const int32_t* p = block + pos + 4 * int64_t(j);
         const int32_t pg = p[0], ps = p[1], leaf = p[2], count = p[3];
@@ -6907,7 +6920,7 @@ __global__ __launch_bounds__(256) void admit_block_records_kernel(
         if (count < 0) neg = 1;
         for (int t = 0; t < nt; t++) {
           const kueue_tas_fits_term tm = terms[tb + t];
-          if (tm.col < 0 || tm.col >= KUEUE_TAS_MAX_COLS) {
+          if (tm.col < 0 || tm.col >= R) {  // (R <= KUEUE_TAS_MAX_COLS: sh_tot's bound too)
             bad |= ABE_COL;
             continue;
           }

@@ -5,7 +5,7 @@
 set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"
 ROOT="$(cd "$HERE/../.." && pwd)"
-OUT="$HERE/_build"
+OUT="${EMU_OUT:-$HERE/_build}"  # (EMU_OUT, EMU_SOURCES_ONLY: build_admit_asan.sh takes the patched copies only)
 mkdir -p "$OUT/src"
 CSRC="$ROOT/kueue_oss_amd/csrc"
 # dynamic LDS: `extern __shared__ T name[];` has no static-local equivalent
@@ -32,6 +32,7 @@ sed "s#\"../../include/#\"#" "$CSRC/tas_internal.h" > "$OUT/src/tas_internal.h"
 cp "$ROOT/include/kueue_tas.h" "$ROOT/include/kueue_tas_debug.h" "$OUT/src/"
 cp "$CSRC/tas_device.hip" "$OUT/src/tas_device.cpp"
 sed "s#\"../../include/#\"#" "$CSRC/tas_host.cpp" > "$OUT/src/tas_host.cpp"
+[ -n "${EMU_SOURCES_ONLY:-}" ] && exit 0
 CXXFLAGS="${CXXFLAGS:--O1 -g}"
 g++ -std=c++17 $CXXFLAGS -ffp-contract=off -fPIC -shared -pthread -I"$HERE" -I"$OUT/src" \
   "$OUT/src/tas_device.cpp" "$OUT/src/tas_host.cpp" "$HERE/hip_emu.cpp" -o "$OUT/libkueue_tas_emu.so"

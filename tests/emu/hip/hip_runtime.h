@@ -246,8 +246,15 @@ struct hipPointerAttribute_t {
   hipMemoryType type;
   int device;
 };
-inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) {
-  a->type = hipMemoryTypeDevice;
+// Every pointer is device memory, except inside a range a test marked as
+// pageable host memory (emu_mark_host_range; emu_clear_host_ranges drops them).
+extern "C" void emu_mark_host_range(const void* ptr, size_t bytes);
+extern "C" void emu_clear_host_ranges();
+namespace emu {
+bool in_host_range(const void* p);
+}
+inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p) {
+  a->type = emu::in_host_range(p) ? hipMemoryTypeUnregistered : hipMemoryTypeDevice;
   a->device = 0;
   return hipSuccess;
 }
@@ -259,8 +266,9 @@ inline hipError_t hipMemcpyToSymbolAsync(const void* sym, const void* s, size_t 
                                          hipStream_t st) {
   return hipMemcpyAsync(static_cast<char*>(const_cast<void*>(sym)) + off, s, n, k, st);
 }
-inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
+inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind) {
   emu::drain_all();
+  if (n && kind == hipMemcpyDeviceToHost && emu::in_host_range(s)) return 1;  // a device copy from pageable host memory
   if (n) memmove(d, s, n);
   return hipSuccess;
 }

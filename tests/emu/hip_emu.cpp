@@ -60,6 +60,16 @@ void fiber_main() {
 }
 }  // namespace
 
+std::vector<std::pair<const char*, size_t>>& host_ranges() {
+  static std::vector<std::pair<const char*, size_t>> v;
+  return v;
+}
+bool in_host_range(const void* p) {
+  for (auto& r : host_ranges())
+    if (static_cast<const char*>(p) >= r.first && static_cast<const char*>(p) < r.first + r.second) return true;
+  return false;
+}
+
 Ctx* cur() { return &g_cur->c; }
 void* dynamic_lds() { return g_lds.data(); }
 
@@ -165,3 +175,8 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& fn
       }
 }
 }  // namespace emu
+
+extern "C" __attribute__((visibility("default"))) void emu_mark_host_range(const void* ptr, size_t bytes) {
+  emu::host_ranges().push_back({static_cast<const char*>(ptr), bytes});
+}
+extern "C" __attribute__((visibility("default"))) void emu_clear_host_ranges() { emu::host_ranges().clear(); }
