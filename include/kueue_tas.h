@@ -274,6 +274,51 @@ int kueue_tas_snapshot_set_leaf_attrs(kueue_tas_ctx* ctx, const int32_t* leaves,
  * kueue_tas_snapshot_load puts every leaf in. */
 int kueue_tas_snapshot_set_leaf_live(kueue_tas_ctx* ctx, const int32_t* leaves, size_t n, const int32_t* live);
 
+/* ---- what the device holds: digest and readback ---------------------------
+ * The resident snapshot is changed in place by the load, apply_deltas,
+ * set_free, set_leaf_attrs, set_leaf_live, splice, set_leaf_tags and the
+ * admit calls; these two read it back, ordered after everything already
+ * enqueued on the context's stream, each returning its result in one copy.
+ *
+ * Digest: with (all uint64, wrapping)
+ *   mix(x):  x ^= x>>30; x *= 0xbf58476d1ce4e5b9; x ^= x>>27; x *= 0x94d049bb133111eb; x ^= x>>31
+ *   elem(kind, i, v) = mix(v ^ mix((kind << 56) | i))
+ * a component is the SUM of elem over its elements (i = leaf index; int32
+ * values sign-extended), in this order, *len = 4 + 2 R + K words:
+ *   topology (kind 1)  the int32 sequence L, N, R, K, lowest_is_hostname,
+ *                      level_sizes[L], child_offsets (as loaded), then per
+ *                      level each domain's id rank (its index when the
+ *                      snapshot was loaded without ranks); i = position
+ *   live     (kind 2)  every leaf OUT of the snapshot: elem(2, i, 1)
+ *   taints   (kind 3)  live leaves: their profile; 0 without a profile array
+ *   tags     (kind 4)  all leaves: their tag; 0 when no leaf tags are set
+ *   free[c]  (kind 5)  live leaves with bit c of free_present: free_capacity
+ *   usage[c] (kind 6)  ALL leaves with bit c of usage_present: tas_usage (a
+ *                      leaf out of the snapshot keeps its usage rows)
+ *   label[k] (kind 7)  live leaves: the value id
+ * A value under a clear presence bit contributes nothing; a present 0
+ * contributes elem(kind, i, 0).  The column index is not an input: two
+ * contexts whose columns are numbered differently compare components by
+ * resource name / label key.  chunks[j] is the sum of every leaf-indexed
+ * contribution (all components but topology) of leaves
+ * [KUEUE_TAS_DIGEST_CHUNK j, KUEUE_TAS_DIGEST_CHUNK (j + 1)), so
+ * sum(chunks) == sum(words[1..]); *n_chunks = ceil(N / KUEUE_TAS_DIGEST_CHUNK).
+ * chunks may be NULL (with n_chunks).  KUEUE_TAS_EOVERFLOW, with *len and
+ * *n_chunks set and nothing else written, when a capacity is short. */
+#define KUEUE_TAS_DIGEST_CHUNK 2048
+int kueue_tas_snapshot_digest(kueue_tas_ctx* ctx, uint64_t* words, size_t cap, size_t* len, uint64_t* chunks,
+                              size_t chunk_cap, size_t* n_chunks);
+/* The stored words of n leaves as they are, unmasked by the presence bits or
+ * the leaf's liveness (leaves == NULL: leaves 0 .. n-1; repeats allowed):
+ * free_rows / usage_rows [n][R] and labels [n][K] in the row layout of
+ * kueue_tas_snapshot_set_free / _set_leaf_attrs, profiles 0 without a profile
+ * array, live 0 for a leaf out of the snapshot, tags 0 when none are set.  Any
+ * output may be NULL.  KUEUE_TAS_EINVAL, with nothing written, for a leaf
+ * outside [0, N) (or n > N with leaves == NULL). */
+int kueue_tas_snapshot_read_leaves(kueue_tas_ctx* ctx, const int32_t* leaves, size_t n, int64_t* free_rows,
+                                   uint32_t* free_present, int64_t* usage_rows, uint32_t* usage_present,
+                                   int32_t* profiles, int32_t* labels, int32_t* live, uint64_t* tags);
+
 /* Evaluate n requests against the resident snapshot.
  *  taint_table:   int32 entries referenced by reqs[i].taint_table (may be NULL if no profiles)
  *  assumed:       overlay records referenced by reqs[i].assumed_begin/end
@@ -778,6 +823,36 @@ int kueue_tas_resource_quantity_string(const char* name, int64_t value, char* bu
  *    device snapshot first. */
 kueue_tas_ctx* kueue_tas_host_ctx(kueue_tas_host* h);
 int kueue_tas_host_leaf_ids(kueue_tas_host* h, char** out_json);
+/* ---- what the device holds, against the host mirror ------------------------
+ * Both calls first bring the device up to date exactly as the next
+ * evaluation would find it (a pending reload or splice; the mirror takes the
+ * usage the device applied on its own).
+ *  snapshot_digest: kueue_tas_snapshot_digest of the host snapshot's context,
+ *    keyed by NAME (two ranks may number their columns differently):
+ *    {"leaves": N, "chunkLeaves": 2048, "topology": w, "live": w, "taints": w,
+ *     "tags": w, "free": {resource: w}, "usage": {resource: w},
+ *     "labels": {label key: w}, "chunks": [w per 2048 leaves], "tree": w,
+ *     "chunksUntagged": [w per 2048 leaves]}, every w 16 hex digits
+ *    (kueue_tas_free).  "tree" is the topology word without its R and K
+ *    elements and "chunksUntagged" the chunk words without the leaf tags'
+ *    part (the host layer's tags are addresses of this process): what
+ *    replicas in other processes, whose column sets may differ, compare;
+ *  verify_device: the same words computed from the host mirror — from exactly
+ *    the arrays a reload would load, plus the leaves out of the snapshot and
+ *    the leaf tags — compared with the device's: {"ok": bool, "components":
+ *    [names that differ: topology, live, taints, tags, free:<resource>,
+ *    usage:<resource>, label:<key>], "mismatchedLeaves": n, "leaves":
+ *    [{"leaf": i, "id": DomainID, "fields": [component names]}]} (at most the
+ *    first 64 leaves listed).  The differing leaves are found from the chunk
+ *    words: only those chunks are read back (kueue_tas_snapshot_read_leaves)
+ *    and compared field by field, over what the digest covers.
+ *    The mirror's usage is itself copied from the device (its shadow diff,
+ *    kueue_tas_snapshot_usage_mark / _usage_changes), the device being the
+ *    authority for usage: the usage comparison checks that mechanism, not an
+ *    independent truth.  Free capacity, taint profiles, labels, liveness and
+ *    the tree are pushed by the host and are checked against it. */
+int kueue_tas_host_snapshot_digest(kueue_tas_host* h, char** out_json);
+int kueue_tas_host_verify_device(kueue_tas_host* h, char** out_json);
 int kueue_tas_host_compile_workload(kueue_tas_host* h, const char* podsets_json, int32_t simulate_empty,
                                     kueue_tas_eval_req* reqs, size_t reqs_cap, size_t* n_groups, int32_t* taint_table,
                                     size_t taint_cap, size_t* taint_len, int32_t* num_taints,

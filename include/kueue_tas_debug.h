@@ -73,6 +73,10 @@ int64_t kueue_tas_merge_reruns(kueue_tas_ctx* ctx);
  * lifetime count of chunks re-run with unbounded select lists after a
  * bounded list overflowed. */
 int kueue_tas_select_groups(kueue_tas_ctx* ctx, int64_t* last_groups, int64_t* scratch_reruns);
+/* Device time of the last kueue_tas_snapshot_digest (ms, HIP events on the
+ * context's stream, recorded while stage timing is on): [0] its two launches,
+ * [1] the launches and the copy of the words to the host. */
+int kueue_tas_last_digest_ms(kueue_tas_ctx* ctx, float* ms2);
 
 /* Work counters of the last kueue_tas_eval_batch: [0] evals whose phase 1
  * (fill + roll-up) ran (one per distinct phase-1 input), [1] evals with

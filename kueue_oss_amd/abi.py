@@ -110,6 +110,21 @@ class EvalOut(c.Structure):  # kueue_tas_eval_out
     ]
 
 
+class SpliceDesc(c.Structure):  # kueue_tas_splice_desc
+    _fields_ = [
+        ("topo", c.POINTER(SnapshotDesc)),
+        ("leaf_src", c.POINTER(c.c_int32)),
+        ("num_new", c.c_int32),
+        ("new_free_capacity", c.POINTER(c.c_int64)),
+        ("new_tas_usage", c.POINTER(c.c_int64)),
+        ("new_free_present", c.POINTER(c.c_uint32)),
+        ("new_usage_present", c.POINTER(c.c_uint32)),
+        ("new_taint_profile", c.POINTER(c.c_int32)),
+        ("new_label_values", c.POINTER(c.c_int32)),
+        ("new_leaf_tags", c.POINTER(c.c_uint64)),
+    ]
+
+
 class FitsReq(c.Structure):  # kueue_tas_fits_req
     _fields_ = [("leaf", c.c_int32), ("count", c.c_int32), ("term_begin", c.c_int32), ("num_terms", c.c_int32)]
 
@@ -161,4 +176,57 @@ def bind_device_layer(lib):
                                                   P(c.c_int32), c.c_size_t, P(c.c_int32), P(c.c_int32), c.c_size_t,
                                                   P(c.c_size_t), P(P(Delta)), P(c.c_size_t)]
     lib.kueue_tas_admit_block_targets.restype = c.c_int
+    lib.kueue_tas_snapshot_set_free.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    lib.kueue_tas_snapshot_set_free.restype = c.c_int
+    lib.kueue_tas_snapshot_set_leaf_attrs.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+    lib.kueue_tas_snapshot_set_leaf_attrs.restype = c.c_int
+    lib.kueue_tas_snapshot_set_leaf_live.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p]
+    lib.kueue_tas_snapshot_set_leaf_live.restype = c.c_int
+    lib.kueue_tas_snapshot_set_leaf_tags.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t]
+    lib.kueue_tas_snapshot_set_leaf_tags.restype = c.c_int
+    lib.kueue_tas_snapshot_splice.argtypes = [c.c_void_p, P(SpliceDesc)]
+    lib.kueue_tas_snapshot_splice.restype = c.c_int
+    lib.kueue_tas_snapshot_digest.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, P(c.c_size_t), c.c_void_p, c.c_size_t,
+                                              P(c.c_size_t)]
+    lib.kueue_tas_snapshot_digest.restype = c.c_int
+    lib.kueue_tas_snapshot_read_leaves.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t] + [c.c_void_p] * 8
+    lib.kueue_tas_snapshot_read_leaves.restype = c.c_int
+    lib.kueue_tas_last_digest_ms.argtypes = [c.c_void_p, P(c.c_float)]
+    lib.kueue_tas_last_digest_ms.restype = c.c_int
     return lib
+
+
+DIGEST_CHUNK = 2048  # KUEUE_TAS_DIGEST_CHUNK
+DIGEST_FIXED = ("topology", "live", "taints", "tags")  # then free[R], usage[R], label[K]
+
+
+def snapshot_digest(lib, ctx):
+    """kueue_tas_snapshot_digest of a raw context: (words, chunk words) as numpy uint64."""
+    import numpy as np
+    n, nc = c.c_size_t(), c.c_size_t()
+    rc = lib.kueue_tas_snapshot_digest(ctx, None, 0, c.byref(n), None, 0, c.byref(nc))
+    if rc not in (0, -5):
+        raise RuntimeError(f"kueue_tas_snapshot_digest failed ({rc}): {lib.kueue_tas_last_error(ctx).decode()}")
+    words = np.zeros(n.value, dtype=np.uint64)
+    chunks = np.zeros(max(nc.value, 1), dtype=np.uint64)
+    rc = lib.kueue_tas_snapshot_digest(ctx, words.ctypes.data, words.size, c.byref(n), chunks.ctypes.data, chunks.size,
+                                       c.byref(nc))
+    if rc:
+        raise RuntimeError(f"kueue_tas_snapshot_digest failed ({rc}): {lib.kueue_tas_last_error(ctx).decode()}")
+    return words, chunks[: nc.value]
+
+
+def read_leaves(lib, ctx, leaves, n, R, K):
+    """kueue_tas_snapshot_read_leaves of a raw context (``leaves`` None: leaves
+    0 .. n-1): dict of numpy arrays free [n, R], free_present, usage [n, R],
+    usage_present, profiles, labels [n, K], live, tags."""
+    import numpy as np
+    ids = None if leaves is None else np.ascontiguousarray(leaves, dtype=np.int32)
+    out = dict(free=np.zeros((n, R), np.int64), free_present=np.zeros(n, np.uint32), usage=np.zeros((n, R), np.int64),
+               usage_present=np.zeros(n, np.uint32), profiles=np.zeros(n, np.int32), labels=np.zeros((n, K), np.int32),
+               live=np.zeros(n, np.int32), tags=np.zeros(n, np.uint64))
+    rc = lib.kueue_tas_snapshot_read_leaves(ctx, None if ids is None else ids.ctypes.data, n,
+                                            *[a.ctypes.data for a in out.values()])
+    if rc:
+        raise RuntimeError(f"kueue_tas_snapshot_read_leaves failed ({rc}): {lib.kueue_tas_last_error(ctx).decode()}")
+    return out

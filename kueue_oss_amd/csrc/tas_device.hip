@@ -430,6 +430,16 @@ struct kueue_tas_ctx {
   std::vector<int32_t> req_local_cls, part_map;
   std::vector<size_t> part_base;
   std::vector<PartClasses> part_cls;
+  // (behind everything the evaluation path reads: that path's members keep their places)
+  // kueue_tas_snapshot_digest: the blocks' partial rows, then the words and chunk words (one D2H);
+  // kueue_tas_snapshot_read_leaves: the requested leaves and the gathered staging block (one D2H)
+  DevBuf<uint64_t> d_digest;
+  HostBuf<uint64_t> h_digest;
+  DevBuf<int32_t> d_read_ids;
+  DevBuf<uint8_t> d_read;
+  HostBuf<uint8_t> h_read;
+  hipEvent_t ev_digest[3] = {};  // before the launches, after them, after the D2H (kueue_tas_last_digest_ms)
+  float digest_ms[2] = {0, 0};
 };
 
 // The leaf-row scatter kernels write repeated entries in no fixed order:
@@ -582,6 +592,8 @@ void kueue_tas_ctx_destroy(kueue_tas_ctx* c) {
   for (auto& e : c->evs)
     if (e) (void)hipEventDestroy(e);
   if (c->ev_deltas) (void)hipEventDestroy(c->ev_deltas);
+  for (auto& e : c->ev_digest)
+    if (e) (void)hipEventDestroy(e);
   if (c->stream3) (void)hipStreamDestroy(c->stream3);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -4087,6 +4099,96 @@ int kueue_tas_snapshot_set_leaf_tags(kueue_tas_ctx* c, const uint64_t* tags, siz
   if (n) HIPCHK(c, hipMemcpyAsync(c->d_leaf_tags.p, tags, n * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->leaf_tags_on = true;
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_snapshot_digest(kueue_tas_ctx* c, uint64_t* words, size_t cap, size_t* len, uint64_t* chunks,
+                              size_t chunk_cap, size_t* n_chunks) {
+  if (!c) return KUEUE_TAS_EINVAL;
+  if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
+  if (!len || (!words && cap) || (chunks && !n_chunks)) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+  const DevSnap& s = c->snap;
+  const size_t C = size_t(kDigestFixed + 2 * s.R + s.K);
+  const size_t nch = (size_t(s.N) + kDigestChunk - 1) / kDigestChunk;
+  *len = C;
+  if (n_chunks) *n_chunks = nch;
+  if (cap < C || (chunks && chunk_cap < nch)) return fail(c, KUEUE_TAS_EOVERFLOW, "digest: capacity");
+  size_t seq = 5 + size_t(s.L);  // the topology sequence (digest_topology_value)
+  for (int l = 0; l < s.L; l++) seq += size_t(s.level_size[l]) + (l + 1 < s.L ? size_t(s.level_size[l]) + 1 : 0);
+  const size_t ntopo = (seq + kDigestChunk - 1) / kDigestChunk;
+  const size_t n_part = nch * C + ntopo, n_out = C + nch;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, c->d_digest.reserve(n_part + n_out));
+  HIPCHK(c, c->h_digest.reserve(n_out));
+  const bool timed = c->stage_timing;
+  if (timed) {
+    for (auto& e : c->ev_digest)
+      if (!e) HIPCHK(c, hipEventCreate(&e));
+    HIPCHK(c, hipEventRecord(c->ev_digest[0], c->stream));
+  }
+  uint64_t* d_out = c->d_digest.p + n_part;
+  hipLaunchKernelGGL(snapshot_digest_kernel, dim3(unsigned(nch + ntopo)), dim3(kDigestThreads), 0, c->stream, s,
+                     c->leaf_tags_on ? c->d_leaf_tags.p : nullptr, int(nch), c->d_digest.p);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(snapshot_digest_sum_kernel, dim3(1), dim3(kDigestThreads), 0, c->stream, c->d_digest.p, int(nch),
+                     int(ntopo), int(C), d_out);
+  HIPCHK(c, hipGetLastError());
+  if (timed) HIPCHK(c, hipEventRecord(c->ev_digest[1], c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_digest.p, d_out, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+  if (timed) HIPCHK(c, hipEventRecord(c->ev_digest[2], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (timed) {
+    (void)hipEventElapsedTime(&c->digest_ms[0], c->ev_digest[0], c->ev_digest[1]);
+    (void)hipEventElapsedTime(&c->digest_ms[1], c->ev_digest[0], c->ev_digest[2]);
+  }
+  memcpy(words, c->h_digest.p, C * 8);
+  if (chunks && nch) memcpy(chunks, c->h_digest.p + C, nch * 8);
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_last_digest_ms(kueue_tas_ctx* c, float* ms2) {
+  if (!c || !ms2) return KUEUE_TAS_EINVAL;
+  ms2[0] = c->digest_ms[0];
+  ms2[1] = c->digest_ms[1];
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_snapshot_read_leaves(kueue_tas_ctx* c, const int32_t* leaves, size_t n, int64_t* free_rows,
+                                   uint32_t* free_present, int64_t* usage_rows, uint32_t* usage_present,
+                                   int32_t* profiles, int32_t* labels, int32_t* live, uint64_t* tags) {
+  if (!c) return KUEUE_TAS_EINVAL;
+  if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
+  const DevSnap& s = c->snap;
+  if (n > size_t(0x7fffffff) || (!leaves && n > size_t(s.N))) return fail(c, KUEUE_TAS_EINVAL, "read_leaves: n");
+  for (size_t i = 0; leaves && i < n; i++)
+    if (leaves[i] < 0 || leaves[i] >= s.N) return fail(c, KUEUE_TAS_EINVAL, "read_leaves: leaf out of range");
+  if (n == 0) return KUEUE_TAS_OK;
+  const size_t R = size_t(s.R), K = size_t(s.K);
+  // the staging block (read_leaves_kernel): free | usage | tags | free_present | usage_present | profiles | live | labels
+  const size_t o_usage = n * R * 8, o_tags = 2 * o_usage, o_fp = o_tags + n * 8, o_up = o_fp + n * 4, o_prof = o_up + n * 4,
+               o_live = o_prof + n * 4, o_lab = o_live + n * 4, bytes = o_lab + n * K * 4;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, c->d_read.reserve(bytes));
+  HIPCHK(c, c->h_read.reserve(bytes));
+  if (leaves) {
+    HIPCHK(c, c->d_read_ids.reserve(n));
+    HIPCHK(c, hipMemcpyAsync(c->d_read_ids.p, leaves, n * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  hipLaunchKernelGGL(read_leaves_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, c->stream, s,
+                     c->leaf_tags_on ? c->d_leaf_tags.p : nullptr, leaves ? c->d_read_ids.p : nullptr, int(n),
+                     c->d_read.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(c->h_read.p, c->d_read.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // (also: the caller's leaf list is read)
+  const uint8_t* h = c->h_read.p;
+  if (free_rows && R) memcpy(free_rows, h, n * R * 8);
+  if (usage_rows && R) memcpy(usage_rows, h + o_usage, n * R * 8);
+  if (tags) memcpy(tags, h + o_tags, n * 8);
+  if (free_present) memcpy(free_present, h + o_fp, n * 4);
+  if (usage_present) memcpy(usage_present, h + o_up, n * 4);
+  if (profiles) memcpy(profiles, h + o_prof, n * 4);
+  if (live) memcpy(live, h + o_live, n * 4);
+  if (labels && K) memcpy(labels, h + o_lab, n * K * 4);
   return KUEUE_TAS_OK;
 }
 

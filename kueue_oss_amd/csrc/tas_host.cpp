@@ -44,6 +44,8 @@
 #include "label_selectors.h"
 #include "tas_balanced.h"
 #include "tas_pool.h"
+#define KTAS_INTERNAL_HOST_ONLY 1
+#include "tas_internal.h"  // the one statement of the snapshot digest (digest_elem), shared with the kernels
 
 static double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -1799,6 +1801,256 @@ class FlavorSnapshot {
     return recolumn();
   }
 
+  // What a reload would load: the descriptor's arrays from the host mirror.
+  // upload() loads exactly these, and mirror_digest() digests exactly these
+  // (plus leafDead and the leaf tags), so "the mirror's view of the device" has
+  // one statement.
+  struct LoadArrays {
+    std::vector<int32_t> sizes, co, ranks, labPacked;
+    std::vector<int64_t> fr, us;  // [R][N]
+    std::vector<uint32_t> fp, up;
+  };
+  kueue_tas_snapshot_desc load_arrays(LoadArrays& a) const {
+    const int L = this->L(), N = this->N(), R = int(cols.size());
+    a.sizes.resize(size_t(L));
+    for (int l = 0; l < L; l++) a.sizes[size_t(l)] = int32_t(values[size_t(l)].size());
+    for (int l = 0; l + 1 < L; l++) a.co.insert(a.co.end(), childOff[size_t(l)].begin(), childOff[size_t(l)].end());
+    a.fr.assign(size_t(R) * size_t(N), 0);
+    a.us.assign(size_t(R) * size_t(N), 0);
+    a.fp.assign(size_t(N), 0);
+    a.up.assign(size_t(N), 0);
+    parallel_ranges(size_t(N), 8192, [&](size_t b, size_t e) {
+      for (size_t i = b; i < e; i++) {  // resources without a column are read by no request (wanted_columns)
+        for (auto& kv : freeCap[i]) {
+          const auto c = colByName.find(kv.first);
+          if (c == colByName.end()) continue;
+          a.fr[size_t(c->second) * size_t(N) + i] = kv.second;
+          a.fp[i] |= 1u << c->second;
+        }
+        for (auto& kv : tasUsage[i]) {
+          const auto c = colByName.find(kv.first);
+          if (c == colByName.end()) continue;
+          a.us[size_t(c->second) * size_t(N) + i] = kv.second;
+          a.up[i] |= 1u << c->second;
+        }
+      }
+    });
+    for (int l = 0; l < L; l++) a.ranks.insert(a.ranks.end(), idRank[size_t(l)].begin(), idRank[size_t(l)].end());
+    kueue_tas_snapshot_desc d{};
+    d.num_levels = L;
+    d.level_sizes = a.sizes.data();
+    d.child_offsets = a.co.data();
+    d.num_cols = R;
+    d.free_capacity = a.fr.data();
+    d.tas_usage = a.us.data();
+    d.free_present = a.fp.data();
+    d.usage_present = a.up.data();
+    d.lowest_is_hostname = lowestIsHostname ? 1 : 0;
+    d.taint_profile = leafProfile.data();
+    d.num_label_cols = int32_t(labelKeys.size());
+    if (!labelValues.empty() && labStride != size_t(N)) {  // [K][N] for the load
+      a.labPacked.resize(labelKeys.size() * size_t(N));
+      for (size_t k = 0; k < labelKeys.size(); k++)
+        memcpy(a.labPacked.data() + k * size_t(N), labelValues.data() + k * labStride, size_t(N) * 4);
+    }
+    d.label_values = labelValues.empty() ? nullptr : labStride != size_t(N) ? a.labPacked.data() : labelValues.data();
+    d.domain_id_rank = a.ranks.data();
+    return d;
+  }
+  // The leaf tags set_tags() gives the device (empty: none).
+  std::vector<uint64_t> mirror_tags() const {
+    std::vector<uint64_t> tags;
+    if (!tagsSet || (cfg.flags & KUEUE_TAS_CFG_HOST_VALUES)) return tags;
+    const int32_t lvl = lowestIsHostname ? L() - 1 : 0;
+    const std::string* const* lv = leaf_values();
+    tags.resize(size_t(N()));
+    for (size_t i = 0; i < tags.size(); i++) tags[i] = uint64_t(reinterpret_cast<uintptr_t>(lv[i] + lvl));
+    return tags;
+  }
+  // kueue_tas_snapshot_digest's words and chunk words of the arrays a reload
+  // would load (a plain loop: the digest's sums commute).
+  void mirror_digest(const kueue_tas_snapshot_desc& d, const std::vector<uint64_t>& tags, std::vector<uint64_t>& words,
+                     std::vector<uint64_t>& chunks) const {
+    using namespace ktas;
+    const size_t N = size_t(this->N()), R = size_t(d.num_cols), K = size_t(d.num_label_cols);
+    words.assign(size_t(kDigestFixed) + 2 * R + K, 0);
+    chunks.assign((N + kDigestChunk - 1) / kDigestChunk, 0);
+    uint64_t pos = 0;
+    auto topo = [&](int32_t v) { words[0] += digest_elem(kDigestTopology, pos++, digest_i32(v)); };
+    topo(d.num_levels);
+    topo(int32_t(N));
+    topo(d.num_cols);
+    topo(d.num_label_cols);
+    topo(d.lowest_is_hostname);
+    size_t sd = 0, nco = 0;
+    for (int l = 0; l < d.num_levels; l++) {
+      topo(d.level_sizes[l]);
+      sd += size_t(d.level_sizes[l]);
+      if (l + 1 < d.num_levels) nco += size_t(d.level_sizes[l]) + 1;
+    }
+    for (size_t i = 0; i < nco; i++) topo(d.child_offsets[i]);
+    for (size_t i = 0; i < sd; i++) topo(d.domain_id_rank[i]);
+    auto add = [&](size_t w, size_t i, uint64_t e) {
+      words[w] += e;
+      chunks[i / kDigestChunk] += e;
+    };
+    for (size_t i = 0; i < N; i++) {
+      const bool live = !leafDead[i];
+      if (!live) add(1, i, digest_elem(kDigestLive, i, 1));
+      if (live && d.taint_profile) add(2, i, digest_elem(kDigestTaint, i, digest_i32(d.taint_profile[i])));
+      if (!tags.empty()) add(3, i, digest_elem(kDigestTag, i, tags[i]));
+      for (size_t c = 0; c < R; c++) {
+        if (live && ((d.free_present[i] >> c) & 1u))
+          add(kDigestFixed + c, i, digest_elem(kDigestFree, i, uint64_t(d.free_capacity[c * N + i])));
+        if ((d.usage_present[i] >> c) & 1u)
+          add(kDigestFixed + R + c, i, digest_elem(kDigestUsage, i, uint64_t(d.tas_usage[c * N + i])));
+      }
+      for (size_t k = 0; k < K && live && d.label_values; k++)
+        add(kDigestFixed + 2 * R + k, i, digest_elem(kDigestLabel, i, digest_i32(d.label_values[k * N + i])));
+    }
+  }
+  // Component names in word order: the fixed four, then free:<resource>,
+  // usage:<resource> (column order = resource-name order) and label:<key>.
+  std::vector<std::string> digest_names() const {
+    std::vector<std::string> n{"topology", "live", "taints", "tags"};
+    for (auto& c : cols) n.push_back("free:" + c);
+    for (auto& c : cols) n.push_back("usage:" + c);
+    for (auto& k : labelKeys) n.push_back("label:" + k);
+    return n;
+  }
+  // The device brought up to date as the next evaluation would find it (a
+  // pending reload or splice; the mirror takes what the device applied on its
+  // own), then its digest.
+  int device_digest(std::vector<uint64_t>& words, std::vector<uint64_t>& chunks) {
+    int rc = upload();
+    if (rc) return rc;
+    flush_mirror();
+    words.assign(size_t(ktas::kDigestFixed) + 2 * cols.size() + labelKeys.size(), 0);
+    chunks.assign((size_t(N()) + ktas::kDigestChunk - 1) / ktas::kDigestChunk, 0);
+    size_t len = 0, nch = 0;
+    rc = kueue_tas_snapshot_digest(ctx, words.data(), words.size(), &len, chunks.data(), chunks.size(), &nch);
+    if (rc || len != words.size() || nch != chunks.size()) {
+      err = std::string("snapshot digest: ") + (rc ? kueue_tas_last_error(ctx) : "the device holds other columns");
+      return rc ? rc : KUEUE_TAS_EINVAL;
+    }
+    return 0;
+  }
+  static std::string hex64(uint64_t v) {
+    char b[24];
+    snprintf(b, sizeof b, "\"%016llx\"", static_cast<unsigned long long>(v));
+    return b;
+  }
+  int digest_json(std::string& o) {
+    std::vector<uint64_t> w, ch;
+    const int rc = device_digest(w, ch);
+    if (rc) return rc;
+    const size_t R = cols.size(), K = labelKeys.size();
+    o = "{\"leaves\":" + std::to_string(N()) + ",\"chunkLeaves\":" + std::to_string(KUEUE_TAS_DIGEST_CHUNK);
+    o += ",\"topology\":" + hex64(w[0]) + ",\"live\":" + hex64(w[1]) + ",\"taints\":" + hex64(w[2]) +
+         ",\"tags\":" + hex64(w[3]);
+    auto map = [&](const char* key, const std::vector<std::string>& names, size_t base) {
+      o += std::string(",\"") + key + "\":{";
+      for (size_t i = 0; i < names.size(); i++) {
+        if (i) o += ",";
+        kjson::write_string(o, names[i]);
+        o += ":" + hex64(w[base + i]);
+      }
+      o += "}";
+    };
+    map("free", cols, size_t(ktas::kDigestFixed));
+    map("usage", cols, size_t(ktas::kDigestFixed) + R);
+    map("labels", labelKeys, size_t(ktas::kDigestFixed) + 2 * R);
+    o += ",\"chunks\":[";
+    for (size_t j = 0; j < ch.size(); j++) o += (j ? "," : "") + hex64(ch[j]);
+    // what replicas in other processes share: the topology word without its R
+    // and K elements (their column sets may differ), and the chunk words
+    // without the leaf tags' part (the tags are this process's addresses; the
+    // sums are linear, so the parts subtract exactly)
+    using namespace ktas;
+    o += "],\"tree\":" + hex64(w[0] - digest_elem(kDigestTopology, 2, digest_i32(int32_t(R))) -
+                              digest_elem(kDigestTopology, 3, digest_i32(int32_t(K))));
+    const std::vector<uint64_t> tags = mirror_tags();
+    for (size_t i = 0; i < tags.size(); i++) ch[i / kDigestChunk] -= digest_elem(kDigestTag, i, tags[i]);
+    o += ",\"chunksUntagged\":[";
+    for (size_t j = 0; j < ch.size(); j++) o += (j ? "," : "") + hex64(ch[j]);
+    o += "]}";
+    return 0;
+  }
+  // kueue_tas_host_verify_device: the mirror's digest against the device's;
+  // where chunk words differ, those chunks' leaves are read back and compared
+  // field by field, over what the digest covers.
+  int verify_json(std::string& o) {
+    std::vector<uint64_t> dw, dch, mw, mch;
+    int rc = device_digest(dw, dch);
+    if (rc) return rc;
+    LoadArrays a;
+    const kueue_tas_snapshot_desc d = load_arrays(a);
+    const std::vector<uint64_t> tags = mirror_tags();
+    mirror_digest(d, tags, mw, mch);
+    const std::vector<std::string> names = digest_names();
+    std::vector<std::string> comps;
+    for (size_t i = 0; i < mw.size(); i++)
+      if (mw[i] != dw[i]) comps.push_back(names[i]);
+    const size_t N = size_t(this->N()), R = cols.size(), K = labelKeys.size();
+    std::vector<int32_t> ls;
+    for (size_t j = 0; j < mch.size(); j++)
+      if (mch[j] != dch[j])
+        for (size_t i = j * KUEUE_TAS_DIGEST_CHUNK; i < std::min(N, (j + 1) * KUEUE_TAS_DIGEST_CHUNK); i++)
+          ls.push_back(int32_t(i));
+    size_t bad = 0;
+    std::string list;
+    if (!ls.empty()) {
+      const size_t n = ls.size();
+      std::vector<int64_t> fr(n * R), us(n * R);
+      std::vector<uint32_t> fp(n), up(n);
+      std::vector<int32_t> prof(n), lab(n * K), live(n);
+      std::vector<uint64_t> tg(n);
+      rc = kueue_tas_snapshot_read_leaves(ctx, ls.data(), n, fr.data(), fp.data(), us.data(), up.data(), prof.data(),
+                                          lab.data(), live.data(), tg.data());
+      if (rc) {
+        err = std::string("read leaves: ") + kueue_tas_last_error(ctx);
+        return rc;
+      }
+      for (size_t q = 0; q < n; q++) {
+        const size_t i = size_t(ls[q]);
+        std::vector<std::string> f;
+        const bool mlive = !leafDead[i], dlive = live[q] != 0;
+        if (mlive != dlive) f.push_back("live");
+        const bool both = mlive && dlive;  // a leaf out of the snapshot: only its usage rows and tag are covered
+        if (both && d.taint_profile && d.taint_profile[i] != prof[q]) f.push_back("taints");
+        if (!tags.empty() && tags[i] != tg[q]) f.push_back("tags");
+        for (size_t c = 0; c < R && both; c++) {
+          const bool mp = (d.free_present[i] >> c) & 1u, dp = (fp[q] >> c) & 1u;
+          if (mp != dp || (mp && d.free_capacity[c * N + i] != fr[q * R + c])) f.push_back(names[ktas::kDigestFixed + c]);
+        }
+        for (size_t c = 0; c < R; c++) {
+          const bool mp = (d.usage_present[i] >> c) & 1u, dp = (up[q] >> c) & 1u;
+          if (mp != dp || (mp && d.tas_usage[c * N + i] != us[q * R + c])) f.push_back(names[ktas::kDigestFixed + R + c]);
+        }
+        for (size_t k = 0; k < K && both && d.label_values; k++)
+          if (d.label_values[k * N + i] != lab[q * K + k]) f.push_back(names[ktas::kDigestFixed + 2 * R + k]);
+        if (f.empty()) continue;
+        if (bad++ >= 64) continue;  // the listing's cap; mismatchedLeaves counts them all
+        list += list.empty() ? "{\"leaf\":" : ",{\"leaf\":";
+        list += std::to_string(i) + ",\"id\":";
+        kjson::write_string(list, leafId[i]);
+        list += ",\"fields\":[";
+        for (size_t k = 0; k < f.size(); k++) {
+          if (k) list += ",";
+          kjson::write_string(list, f[k]);
+        }
+        list += "]}";
+      }
+    }
+    o = std::string("{\"ok\":") + (comps.empty() && mch == dch ? "true" : "false") + ",\"components\":[";
+    for (size_t i = 0; i < comps.size(); i++) {
+      if (i) o += ",";
+      kjson::write_string(o, comps[i]);
+    }
+    o += "],\"mismatchedLeaves\":" + std::to_string(bad) + ",\"leaves\":[" + list + "]}";
+    return 0;
+  }
+
   int upload() {
     if (!dirty) return splicePending && ctx ? upload_splice() : 0;
     splicePending = false;
@@ -1812,50 +2064,9 @@ class FlavorSnapshot {
       }
       kueue_tas_set_stage_timing(ctx, stageTiming ? 1 : 0);
     }
-    const int L = this->L(), N = this->N(), R = int(cols.size());
-    std::vector<int32_t> sizes(L), co;
-    for (int l = 0; l < L; l++) sizes[l] = int32_t(values[l].size());
-    for (int l = 0; l + 1 < L; l++) co.insert(co.end(), childOff[l].begin(), childOff[l].end());
-    std::vector<int64_t> fr(size_t(R) * N, 0), us(size_t(R) * N, 0);
-    std::vector<uint32_t> fp(N, 0), up(N, 0);
-    parallel_ranges(size_t(N), 8192, [&](size_t a, size_t b) {
-      for (size_t i = a; i < b; i++) {  // resources without a column are read by no request (wanted_columns)
-        for (auto& kv : freeCap[i]) {
-          const auto c = colByName.find(kv.first);
-          if (c == colByName.end()) continue;
-          fr[size_t(c->second) * size_t(N) + i] = kv.second;
-          fp[i] |= 1u << c->second;
-        }
-        for (auto& kv : tasUsage[i]) {
-          const auto c = colByName.find(kv.first);
-          if (c == colByName.end()) continue;
-          us[size_t(c->second) * size_t(N) + i] = kv.second;
-          up[i] |= 1u << c->second;
-        }
-      }
-    });
-    std::vector<int32_t> ranks;
-    for (int l = 0; l < L; l++) ranks.insert(ranks.end(), idRank[l].begin(), idRank[l].end());
-    kueue_tas_snapshot_desc d{};
-    d.num_levels = L;
-    d.level_sizes = sizes.data();
-    d.child_offsets = co.data();
-    d.num_cols = R;
-    d.free_capacity = fr.data();
-    d.tas_usage = us.data();
-    d.free_present = fp.data();
-    d.usage_present = up.data();
-    d.lowest_is_hostname = lowestIsHostname ? 1 : 0;
-    d.taint_profile = leafProfile.data();
-    d.num_label_cols = int32_t(labelKeys.size());
-    std::vector<int32_t> labPacked;  // [K][N] for the load
-    if (!labelValues.empty() && labStride != size_t(N)) {
-      labPacked.resize(labelKeys.size() * size_t(N));
-      for (size_t k = 0; k < labelKeys.size(); k++)
-        memcpy(labPacked.data() + k * size_t(N), labelValues.data() + k * labStride, size_t(N) * 4);
-    }
-    d.label_values = labelValues.empty() ? nullptr : labStride != size_t(N) ? labPacked.data() : labelValues.data();
-    d.domain_id_rank = ranks.data();
+    const int N = this->N();
+    LoadArrays a;
+    const kueue_tas_snapshot_desc d = load_arrays(a);
     int rc = kueue_tas_snapshot_load(ctx, &d);
     if (!rc) rc = kueue_tas_snapshot_usage_mark(ctx);  // device usage == host mirror
     if (rc) {
@@ -5607,6 +5818,34 @@ int kueue_tas_host_leaf_ids(kueue_tas_host* h, char** out_json) {
   }
   *out_json = dup(o + "]");
   return 0;
+}
+
+int kueue_tas_host_snapshot_digest(kueue_tas_host* h, char** out_json) {
+  if (!h || !h->snap || !h->err.empty() || !out_json) return KUEUE_TAS_EINVAL;
+  try {
+    std::string o;
+    const int rc = h->snap->digest_json(o);
+    if (rc) h->err = h->snap->err;
+    else *out_json = dup(o);
+    return rc;
+  } catch (const std::exception& e) {
+    h->err = e.what();
+    return KUEUE_TAS_EINVAL;
+  }
+}
+
+int kueue_tas_host_verify_device(kueue_tas_host* h, char** out_json) {
+  if (!h || !h->snap || !h->err.empty() || !out_json) return KUEUE_TAS_EINVAL;
+  try {
+    std::string o;
+    const int rc = h->snap->verify_json(o);
+    if (rc) h->err = h->snap->err;
+    else *out_json = dup(o);
+    return rc;
+  } catch (const std::exception& e) {
+    h->err = e.what();
+    return KUEUE_TAS_EINVAL;
+  }
 }
 
 int kueue_tas_host_compile_workload(kueue_tas_host* h, const char* podsets_json, int32_t simulate_empty,

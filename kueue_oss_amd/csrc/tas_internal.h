@@ -1,11 +1,60 @@
 // tas_internal.h — device-side data structures shared by the HIP kernels and
 // the C-ABI glue in tas_device.hip.  Not part of the public ABI.
 #pragma once
+// KTAS_INTERNAL_HOST_ONLY (tas_host.cpp, compiled as plain C++ without the HIP
+// headers): only the snapshot digest's statement below.
+#ifndef KTAS_INTERNAL_HOST_ONLY
 #include <hip/hip_runtime.h>
+#else
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#endif
 #include <stdint.h>
 
 #include "../../include/kueue_tas_debug.h"
 
+namespace ktas {
+
+// ---- snapshot digest (kueue_tas_snapshot_digest) ---------------------------
+// The one statement of the hash, shared by snapshot_digest_kernel and the host
+// layer's mirror digest.  A component is the wrapping 64-bit SUM of
+// digest_elem over its elements, so any grid shape or reduction order — and a
+// plain host loop — gives the same word.  `i` is the leaf index (the position
+// in the sequence for the topology component); the column index is not an
+// input: columns are matched by resource name / label key, never by index.
+// int32 values (profiles, label ids, the topology sequence) enter sign-extended.
+enum DigestKind : uint32_t {
+  kDigestTopology = 1,
+  kDigestLive = 2,
+  kDigestTaint = 3,
+  kDigestTag = 4,
+  kDigestFree = 5,
+  kDigestUsage = 6,
+  kDigestLabel = 7,
+};
+constexpr int kDigestChunk = KUEUE_TAS_DIGEST_CHUNK;  // leaves per chunk word (= kLfcChunk)
+constexpr int kDigestFixed = 4;                       // topology, live, taints, tags; then free[R], usage[R], label[K]
+
+__host__ __device__ inline uint64_t digest_mix(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27;
+  x *= 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return x;
+}
+__host__ __device__ inline uint64_t digest_elem(uint32_t kind, uint64_t i, uint64_t v) {
+  return digest_mix(v ^ digest_mix((uint64_t(kind) << 56) | i));
+}
+__host__ __device__ inline uint64_t digest_i32(int32_t v) { return uint64_t(int64_t(v)); }
+
+}  // namespace ktas
+
+#ifndef KTAS_INTERNAL_HOST_ONLY
 namespace ktas {
 
 constexpr int kWave = 64;
@@ -127,6 +176,7 @@ struct LeafPartial {
 // reduce to bin counts: chunk histograms of the leaf values.
 constexpr int kLfcBins = 128;    // values 0..126 exact; bin 127 counts values >= 127
 constexpr int kLfcChunk = 2048;  // leaves per histogram chunk
+static_assert(kDigestChunk == kLfcChunk, "the digest's chunk words cover the LFC chunks");
 
 // Phase-2 result of a fast-LFC greedy eval that the emit kernel expands:
 // every leaf with 0 < value < t, then the first m leaves with value t (index
@@ -226,3 +276,4 @@ struct DevBatch {
 };
 
 }  // namespace ktas
+#endif  // KTAS_INTERNAL_HOST_ONLY

@@ -7094,4 +7094,219 @@ __global__ __launch_bounds__(256) void admit_block_runs_kernel(const int64_t* bo
   }
 }
 
+// ---- snapshot digest and readback (kueue_tas_snapshot_digest / _read_leaves) ----
+// A read-only pass over the resident columns (digest_elem, tas_internal.h).
+// Block j < nchunks takes the leaves of chunk j, eight per thread: thread t
+// reads leaves base + t + 256 q, so consecutive lanes read consecutive leaves
+// of a column (8-byte loads for the capacity columns).  The presence words
+// and the dead map are read once per leaf; a thread's eight loads of a column
+// are issued before any of them is mixed.  Every component is reduced in the
+// wave (DPP / permlane butterfly), then across the four waves through LDS, and
+// the block STORES its row of partial[j][C] (slot 0: the chunk word, slot w:
+// its part of word w) — no atomics, no last block: snapshot_digest_sum_kernel
+// adds the rows.  Blocks nchunks .. take 2048 positions each of the topology
+// sequence and store one partial each behind the rows.
+constexpr int kDigestThreads = 256;
+constexpr int kDigestPerThread = kDigestChunk / kDigestThreads;
+constexpr int kDigestSlots = 64;  // components reduced per LDS round
+
+__device__ __forceinline__ uint64_t digest_wave_sum(uint64_t v) {
+  butterfly(64, [&](auto m) { v += bfly64<decltype(m)::value>(v); });
+  return v;
+}
+
+// Position p of the topology sequence: L, N, R, K, lowest_is_hostname,
+// level_sizes[L], the child offsets as loaded, then every level's id ranks.
+__device__ __forceinline__ int32_t digest_topology_value(const DevSnap& s, int nco, int64_t p) {
+  if (p < 5) return p == 0 ? s.L : p == 1 ? s.N : p == 2 ? s.R : p == 3 ? s.K : s.lowest_is_hostname;
+  p -= 5;
+  if (p < s.L) return s.level_size[p];
+  p -= s.L;
+  if (p < nco) return s.child_off[p];
+  p -= nco;
+  int l = 0;
+  while (l + 1 < s.L && p >= s.level_size[l]) p -= s.level_size[l++];
+  return s.id_rank ? s.id_rank[s.level_off[l] + p] : int32_t(p);
+}
+
+__global__ __launch_bounds__(kDigestThreads) void snapshot_digest_kernel(DevSnap s, const uint64_t* tags, int nchunks,
+                                                                          uint64_t* partial) {
+  __shared__ uint64_t red[kDigestThreads / kWave][kDigestSlots];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int C = kDigestFixed + 2 * s.R + s.K;
+  if (int(blockIdx.x) >= nchunks) {  // the topology sequence
+    int nco = 0;
+    int64_t total = 5 + s.L;
+    for (int l = 0; l < s.L; l++) {
+      if (l + 1 < s.L) nco += s.level_size[l] + 1;
+      total += s.level_size[l];
+    }
+    total += nco;
+    const int tb = int(blockIdx.x) - nchunks;
+    uint64_t acc = 0;
+    for (int q = 0; q < kDigestPerThread; q++) {
+      const int64_t p = int64_t(tb) * kDigestChunk + tid + q * kDigestThreads;
+      if (p < total) acc += digest_elem(kDigestTopology, uint64_t(p), digest_i32(digest_topology_value(s, nco, p)));
+    }
+    acc = digest_wave_sum(acc);
+    if (lane == 0) red[wave][0] = acc;
+    __syncthreads();
+    if (tid == 0) partial[int64_t(nchunks) * C + tb] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+    return;
+  }
+  uint64_t* row = partial + int64_t(blockIdx.x) * C;
+  const int64_t base = int64_t(blockIdx.x) * kDigestChunk + tid;
+  const int64_t N = s.N;
+  // once per leaf: presence words, in-range and dead masks
+  uint32_t fp[kDigestPerThread], up[kDigestPerThread];
+  uint32_t in = 0, dead = 0;
+#pragma unroll
+  for (int q = 0; q < kDigestPerThread; q++) {
+    const int64_t i = base + q * kDigestThreads;
+    const bool ok = i < N;
+    fp[q] = ok ? s.free_present[i] : 0u;
+    up[q] = ok ? s.usage_present[i] : 0u;
+    in |= uint32_t(ok) << q;
+    dead |= uint32_t(ok && s.leaf_dead && s.leaf_dead[i]) << q;
+  }
+  const uint32_t live = in & ~dead;
+  uint64_t chunk = 0;
+  int slot = 0, word = 1;  // LDS slot of the next component, the word slot 0 of this round is
+  auto flush = [&]() {
+    __syncthreads();
+    if (tid < slot) row[word + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    __syncthreads();
+    word += slot;
+    slot = 0;
+  };
+  auto put = [&](uint64_t v) {  // the thread's part of the next component
+    chunk += v;
+    v = digest_wave_sum(v);
+    if (lane == 0) red[wave][slot] = v;
+    if (++slot == kDigestSlots) flush();
+  };
+  {  // live: the leaves out of the snapshot
+    uint64_t v = 0;
+#pragma unroll
+    for (int q = 0; q < kDigestPerThread; q++)
+      if ((dead >> q) & 1u) v += digest_elem(kDigestLive, uint64_t(base + q * kDigestThreads), 1);
+    put(v);
+  }
+  {  // taints
+    int32_t x[kDigestPerThread];
+    uint64_t v = 0;
+    if (s.taint_profile) {
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++) x[q] = (in >> q) & 1u ? s.taint_profile[base + q * kDigestThreads] : 0;
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++)
+        if ((live >> q) & 1u) v += digest_elem(kDigestTaint, uint64_t(base + q * kDigestThreads), digest_i32(x[q]));
+    }
+    put(v);
+  }
+  {  // tags
+    uint64_t x[kDigestPerThread];
+    uint64_t v = 0;
+    if (tags) {
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++) x[q] = (in >> q) & 1u ? tags[base + q * kDigestThreads] : 0;
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++)
+        if ((in >> q) & 1u) v += digest_elem(kDigestTag, uint64_t(base + q * kDigestThreads), x[q]);
+    }
+    put(v);
+  }
+  for (int pass = 0; pass < 2; pass++) {  // free[c] over the live leaves, then usage[c] over all
+    const int64_t* col = pass == 0 ? s.free_cap : s.tas_usage;
+    const uint32_t kind = pass == 0 ? kDigestFree : kDigestUsage;
+    const uint32_t among = pass == 0 ? live : in;
+    for (int c = 0; c < s.R; c++, col += N) {
+      int64_t x[kDigestPerThread];
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++) x[q] = (in >> q) & 1u ? col[base + q * kDigestThreads] : 0;
+      uint64_t v = 0;
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++)
+        if (((among >> q) & 1u) && (((pass == 0 ? fp[q] : up[q]) >> c) & 1u))
+          v += digest_elem(kind, uint64_t(base + q * kDigestThreads), uint64_t(x[q]));
+      put(v);
+    }
+  }
+  for (int k = 0; k < s.K; k++) {  // label[k] over the live leaves
+    int32_t x[kDigestPerThread];
+    uint64_t v = 0;
+    if (s.label_values) {
+      const int32_t* col = s.label_values + int64_t(k) * N;
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++) x[q] = (in >> q) & 1u ? col[base + q * kDigestThreads] : 0;
+#pragma unroll
+      for (int q = 0; q < kDigestPerThread; q++)
+        if ((live >> q) & 1u) v += digest_elem(kDigestLabel, uint64_t(base + q * kDigestThreads), digest_i32(x[q]));
+    }
+    put(v);
+  }
+  flush();
+  chunk = digest_wave_sum(chunk);
+  if (lane == 0) red[wave][0] = chunk;
+  __syncthreads();
+  if (tid == 0) row[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+}
+
+// out[0 .. C): the words (word 0 from the topology partials, word w from slot
+// w of the chunk rows), out[C .. C + nchunks): the chunk words.
+__global__ __launch_bounds__(kDigestThreads) void snapshot_digest_sum_kernel(const uint64_t* partial, int nchunks,
+                                                                              int ntopo, int C, uint64_t* out) {
+  // a word's rows are split over `parts` threads (C3: 19 words x 13 parts), so a thread adds
+  // ~nchunks / parts dependent loads instead of nchunks; the parts meet in LDS
+  __shared__ uint64_t acc[kDigestThreads];
+  const int tid = threadIdx.x;
+  const int parts = C < kDigestThreads ? kDigestThreads / C : 1;
+  for (int w0 = 0; w0 < C; w0 += kDigestThreads) {  // (one pass unless C >= 256)
+    const int w = w0 + (parts > 1 ? tid % C : tid), part = parts > 1 ? tid / C : 0;
+    uint64_t v = 0;
+    if (w < C && part < parts) {
+      if (w == 0)
+        for (int t = part; t < ntopo; t += parts) v += partial[int64_t(nchunks) * C + t];
+      else
+        for (int j = part; j < nchunks; j += parts) v += partial[int64_t(j) * C + w];
+    }
+    acc[tid] = v;
+    __syncthreads();
+    if (part == 0 && w < C) {
+      for (int p = 1; p < parts; p++) v += acc[tid + p * C];
+      out[w] = v;
+    }
+    __syncthreads();
+  }
+  for (int j = tid; j < nchunks; j += kDigestThreads) out[C + j] = partial[int64_t(j) * C];
+}
+
+// kueue_tas_snapshot_read_leaves: one thread per requested leaf gathers its
+// stored words into the staging block (free[n][R] | usage[n][R] | tags[n] |
+// free_present[n] | usage_present[n] | profiles[n] | live[n] | labels[n][K]).
+__global__ void read_leaves_kernel(DevSnap s, const uint64_t* tags, const int32_t* leaves, int n, uint8_t* stage) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int leaf = leaves ? leaves[t] : t;
+  if (leaf < 0 || leaf >= s.N) return;  // (the host rejected it)
+  int64_t* o_free = reinterpret_cast<int64_t*>(stage);
+  int64_t* o_usage = o_free + int64_t(n) * s.R;
+  uint64_t* o_tags = reinterpret_cast<uint64_t*>(o_usage + int64_t(n) * s.R);
+  uint32_t* o_fp = reinterpret_cast<uint32_t*>(o_tags + n);
+  uint32_t* o_up = o_fp + n;
+  int32_t* o_prof = reinterpret_cast<int32_t*>(o_up + n);
+  int32_t* o_live = o_prof + n;
+  int32_t* o_lab = o_live + n;
+  for (int c = 0; c < s.R; c++) {
+    o_free[int64_t(t) * s.R + c] = s.free_cap[int64_t(c) * s.N + leaf];
+    o_usage[int64_t(t) * s.R + c] = s.tas_usage[int64_t(c) * s.N + leaf];
+  }
+  o_tags[t] = tags ? tags[leaf] : 0;
+  o_fp[t] = s.free_present[leaf];
+  o_up[t] = s.usage_present[leaf];
+  o_prof[t] = s.taint_profile ? s.taint_profile[leaf] : 0;
+  o_live[t] = (s.leaf_dead && s.leaf_dead[leaf]) ? 0 : 1;
+  for (int k = 0; k < s.K; k++) o_lab[int64_t(t) * s.K + k] = s.label_values ? s.label_values[int64_t(k) * s.N + leaf] : 0;
+}
+
 }  // namespace ktas

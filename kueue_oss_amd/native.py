@@ -74,6 +74,8 @@ EXPORTED_SYMBOLS = [
     "kueue_tas_last_admit_launches", "kueue_tas_host_last_admit_launches", "kueue_tas_host_last_counters",
     "kueue_tas_eval_generation", "kueue_tas_admit_block_targets", "kueue_tas_host_admit_block_targets",
     "kueue_tas_host_usage_deltas", "kueue_tas_host_last_admit_block_path", "kueue_tas_host_column_generation",
+    "kueue_tas_snapshot_digest", "kueue_tas_snapshot_read_leaves", "kueue_tas_last_digest_ms",
+    "kueue_tas_host_snapshot_digest", "kueue_tas_host_verify_device",
 ]
 
 # the Makefile's SRC_HASH inputs, in order
@@ -249,6 +251,9 @@ def _bind(lib):
     lib.kueue_tas_host_last_admit_block_path.restype = c.c_int
     lib.kueue_tas_host_column_generation.argtypes = [c.c_void_p]
     lib.kueue_tas_host_column_generation.restype = c.c_uint64
+    for name in ("kueue_tas_host_snapshot_digest", "kueue_tas_host_verify_device"):
+        getattr(lib, name).argtypes = [c.c_void_p, c.POINTER(c.c_void_p)]
+        getattr(lib, name).restype = c.c_int
 
 
 def resource_quantity_string(name: str, value: int, lib=None) -> str:
@@ -784,6 +789,45 @@ class TASFlavorSnapshot:
         if self._lib.kueue_tas_host_leaf_ids(self._h, ctypes.byref(out)):
             raise RuntimeError(self._err())
         return _take(self._lib, out)
+
+    # ---- what the device holds (kueue_tas.h "what the device holds") ----
+    def snapshot_digest(self) -> dict:
+        """kueue_tas_host_snapshot_digest: the digest of the resident snapshot,
+        keyed by name: {"leaves", "chunkLeaves", "topology", "live", "taints",
+        "tags", "free": {resource: word}, "usage": {resource: word}, "labels":
+        {key: word}, "chunks": [word]}, every word 16 hex digits."""
+        out = ctypes.c_void_p()
+        rc = self._lib.kueue_tas_host_snapshot_digest(self._h, ctypes.byref(out))
+        if rc:
+            raise RuntimeError(f"kueue_tas_host_snapshot_digest failed ({rc}): {self._err()}")
+        return _take(self._lib, out)
+
+    def verify_device(self) -> dict:
+        """kueue_tas_host_verify_device: the host mirror's digest against the
+        device's; {"ok", "components", "mismatchedLeaves", "leaves": [{"leaf",
+        "id", "fields"}]} (the first 64 differing leaves)."""
+        out = ctypes.c_void_p()
+        rc = self._lib.kueue_tas_host_verify_device(self._h, ctypes.byref(out))
+        if rc:
+            raise RuntimeError(f"kueue_tas_host_verify_device failed ({rc}): {self._err()}")
+        return _take(self._lib, out)
+
+    def read_leaves(self, leaves=None) -> dict:
+        """kueue_tas_snapshot_read_leaves of the resident snapshot (``leaves``
+        None: every leaf): the stored words as they are, unmasked.  {"leaves":
+        indices, "resources": column names, "labelKeys": label column keys,
+        "free" / "usage": int64 [n, R], "free_present" / "usage_present":
+        uint32 [n] (bit c: column c), "profiles", "live": int32 [n], "labels":
+        int32 [n, K], "tags": uint64 [n]}."""
+        import numpy as np
+        from . import abi
+        d = self.snapshot_digest()  # (brings the device up to date; names in column order)
+        res, keys = list(d["free"]), list(d["labels"])
+        abi.bind_device_layer(self._lib)
+        ids = np.arange(d["leaves"], dtype=np.int32) if leaves is None else np.ascontiguousarray(leaves, dtype=np.int32)
+        out = abi.read_leaves(self._lib, self.device_ctx(), None if leaves is None else ids, ids.size, len(res),
+                              len(keys))
+        return dict(out, leaves=ids, resources=res, labelKeys=keys)
 
     def select_groups(self):
         """(slot groups of the last chunk's BestFit select, chunks re-run with

@@ -159,6 +159,99 @@ def broadcast_deltas(deltas, dist, src: int = 0, device=None):
         _grow("deltas", k)
 
 
+def _digest_components(d: dict) -> dict:
+    """A snapshot_digest() as {component name: word}, the names shared across
+    ranks: the tree (topology without R and K), live, taints, and per resource
+    name / label key.  The leaf tags are left out: the host layer's tags are
+    addresses of its own process."""
+    out = {"topology": (d["leaves"], d["tree"]), "live": d["live"], "taints": d["taints"]}
+    for kind, key in (("free", "free"), ("usage", "usage"), ("label", "labels")):
+        for name, w in d[key].items():
+            out[f"{kind}:{name}"] = w
+    return out
+
+
+def _leaf_fields(a: dict, b: dict, i: int, j: int) -> list:
+    """Component names in which row i of rank 0's rows ``a`` and row j of
+    another rank's rows ``b`` (read_leaves() as lists) differ, over what the
+    digest covers and both ranks hold."""
+    f = []
+    if a["live"][i] != b["live"][j]:
+        f.append("live")
+    both = a["live"][i] and b["live"][j]  # a leaf out of the snapshot: only its usage rows are covered
+    if both and a["profiles"][i] != b["profiles"][j]:
+        f.append("taints")
+    for kind, present in (("free", "free_present"), ("usage", "usage_present")):
+        if kind == "free" and not both:
+            continue
+        for ca, name in enumerate(a["resources"]):
+            if name not in b["resources"]:
+                continue
+            cb = b["resources"].index(name)
+            pa, pb = (a[present][i] >> ca) & 1, (b[present][j] >> cb) & 1
+            if pa != pb or (pa and a[kind][i][ca] != b[kind][j][cb]):
+                f.append(f"{kind}:{name}")
+    for ka, key in enumerate(a["labelKeys"]):
+        if both and key in b["labelKeys"] and a["labels"][i][ka] != b["labels"][j][b["labelKeys"].index(key)]:
+            f.append(f"label:{key}")
+    return f
+
+
+def verify_replicas(snap, dist) -> dict:
+    """Prove that every rank's resident snapshot equals rank 0's, or name what
+    differs; the same report on every rank:
+
+        {"ok": bool, "ranks": {rank: [components differing from rank 0]},
+         "leaves": [{"rank", "leaf", "fields"}] (the first 64),
+         "onlyOn": {component name: [ranks holding it]}}
+
+    Every rank's snapshot_digest() is exchanged (all_gather_object: gloo and
+    nccl) and compared with rank 0's per NAME — resource columns exist only for
+    resources some request named, numbered in name order, so ranks may hold
+    different column sets: a resource or label key that a rank lacks is listed
+    under "onlyOn" and is not a mismatch.  When components differ, the ranks
+    exchange the read_leaves() rows of the chunks whose words differ (every
+    chunk, when a column only some ranks hold has contents) and the differing
+    leaves and fields are named.  Collective: every rank calls it."""
+    world, rank = dist.get_world_size(), dist.get_rank()
+    mine = snap.snapshot_digest()
+    digs = [None] * world
+    dist.all_gather_object(digs, mine)
+    comps = [_digest_components(d) for d in digs]
+    names = sorted(set().union(*comps))
+    only_on = {n: [r for r in range(world) if n in comps[r]] for n in names
+               if not all(n in c for c in comps)}
+    ranks = {}
+    for r in range(1, world):
+        diff = [n for n in names if n in comps[0] and n in comps[r] and comps[0][n] != comps[r][n]]
+        if diff:
+            ranks[r] = diff
+    report = {"ok": not ranks, "ranks": ranks, "leaves": [], "onlyOn": only_on}
+    same_n = all(d["leaves"] == digs[0]["leaves"] for d in digs)
+    if not ranks or not same_n:  # (other leaf counts: the trees differ, leaf indices do not correspond)
+        return report
+    # the chunks to read back: the same set on every rank (each holds every digest)
+    zero = "0" * 16
+    partial = any(comps[r][name] != zero for name, rs in only_on.items() for r in rs)
+    nch = len(digs[0]["chunksUntagged"])
+    chunks = [j for j in range(nch)
+              if partial or any(digs[r]["chunksUntagged"][j] != digs[0]["chunksUntagged"][j] for r in ranks)]
+    cl, n = digs[0]["chunkLeaves"], digs[0]["leaves"]
+    leaves = [i for j in chunks for i in range(j * cl, min(n, (j + 1) * cl))]
+    rows = None
+    if rank == 0 or rank in ranks:
+        got = snap.read_leaves(leaves)
+        rows = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in got.items() if k not in ("tags", "leaves")}
+    every = [None] * world
+    dist.all_gather_object(every, rows)
+    for r in sorted(ranks):
+        for q, leaf in enumerate(leaves):
+            f = _leaf_fields(every[0], every[r], q, q)
+            if f and len(report["leaves"]) < 64:
+                report["leaves"].append({"rank": r, "leaf": leaf, "fields": f})
+    return report
+
+
 def admit_round(snap, world: int, rank: int, dist, device=None, src: int = 0, workloads=None, targets=None):
     """One nominate/admit round after every rank's run_compiled: all-gather the
     assignments, rank ``src`` admits in workload order (Fits + AddUsage on its
