@@ -354,6 +354,60 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* ctx, const kueue_tas_eval_req* cons
                               const int32_t* affinity_values, size_t num_affinity_values, kueue_tas_eval_out* out,
                               int64_t* entry_offsets, int32_t* entries, size_t entries_capacity, int32_t* taint_counts,
                               int32_t* res_counts);
+/* ---- removal sets: evaluations under SimulateWorkloadRemoval ----------------
+ * (snapshot.go:67-84 -> removeTASUsage tas_flavor_snapshot.go:281-293; what
+ * preemption's `minimal` and fillBackWorkloads evaluate, preemption.go:307-345).
+ * A removal set is an ordered list of at most KUEUE_TAS_REMOVAL_MAX_CANDIDATES
+ * candidates, each an index into a target table laid out as for
+ * kueue_tas_admit_targets (target t owns target_deltas[target_off[t] ..
+ * target_off[t + 1])); set s lists cand[cand_off[s] .. cand_off[s + 1]).  An
+ * evaluation names a set and a 64-bit mask over the set's positions and is
+ * evaluated as if the masked candidates' usage had left the snapshot: every
+ * delta record (leaf, col, d) of a masked candidate is an assumed record
+ * (leaf, col, -d) in wrapping int64 — the key created as Requests.Sub creates
+ * it, a record with leaf -1 dropped, records of one (leaf, col) not merged
+ * (the fills sum them) — merged by leaf with the request's own assumed records.
+ *
+ * removal_tables_build uploads the target table and the lists once and leaves
+ * one table per set resident on the device (removal_table_kernel: the set's
+ * records gathered, sorted by leaf in LDS); the expansion of a (set, mask)
+ * happens on the device, inside the batch (removal_expand_kernel), so the
+ * host uploads bytes linear in the table, never in the number of masks.  The
+ * single-workgroup sort bounds a set: at most KUEUE_TAS_REMOVAL_SET_CAP records
+ * (those with leaf -1 included) over its candidates.
+ * Returns, with the previous tables unchanged: KUEUE_TAS_EINVAL for offsets
+ * that are not monotone from 0, a target index outside [0, n_targets), more
+ * than 64 candidates in a set, a record's leaf outside [-1, N) or column
+ * outside [0, R); KUEUE_TAS_EOVERFLOW for a set above the record cap (the
+ * caller expands that set's overlays on the host).
+ * The tables stay until the next build, removal_tables_clear, or a load or
+ * splice of the snapshot (leaf indices change): kueue_tas_eval_batch_removals
+ * with a set then returns KUEUE_TAS_EINVAL ("removal tables are stale"). */
+#define KUEUE_TAS_REMOVAL_MAX_CANDIDATES 64
+#define KUEUE_TAS_REMOVAL_SET_CAP 4096
+int kueue_tas_removal_tables_build(kueue_tas_ctx* ctx, const kueue_tas_delta* target_deltas, const int64_t* target_off,
+                                   size_t n_targets, const int32_t* cand, const int64_t* cand_off, size_t n_sets);
+int kueue_tas_removal_tables_clear(kueue_tas_ctx* ctx);
+/* kueue_tas_eval_batch_ptrs with a removal per request: removal_set[i] is a
+ * set of the resident tables (-1: none) and removal_mask[i] the positions
+ * removed (bits at or above the set's candidate count: KUEUE_TAS_EINVAL).
+ * Both NULL, every set -1 or every mask 0: exactly kueue_tas_eval_batch_ptrs.
+ * reqs[i]'s own assumed range is kept (addAssumedUsage chaining).  Requests
+ * whose records, set and mask are equal share their phase 1; no others do.
+ * No host synchronisation is added to the batch. */
+int kueue_tas_eval_batch_removals(kueue_tas_ctx* ctx, const kueue_tas_eval_req* const* reqs, size_t n,
+                                  const int32_t* taint_table, size_t taint_table_len, int32_t num_taints,
+                                  const kueue_tas_assumed* assumed, size_t num_assumed,
+                                  const kueue_tas_affinity_req* affinity, size_t num_affinity,
+                                  const int32_t* affinity_values, size_t num_affinity_values, kueue_tas_eval_out* out,
+                                  int64_t* entry_offsets, int32_t* entries, size_t entries_capacity,
+                                  int32_t* taint_counts, int32_t* res_counts, const int32_t* removal_set,
+                                  const uint64_t* removal_mask);
+/* What the last build left and the removal evaluations since cost: [0] sets,
+ * [1] table records resident, [2] bytes the build uploaded, [3] assumed
+ * records expanded on the device since the build (summed over evaluations). */
+int kueue_tas_removal_stats(kueue_tas_ctx* ctx, int64_t out[4]);
+
 /* Phase-1 counters of request i of the last kueue_tas_eval_batch (its
  * fillInCounts + fillInCountsHelper result, tas_flavor_snapshot.go:1568-1719):
  * out[f * S + g] for field f = state, sliceState, stateWithLeader,
@@ -760,6 +814,54 @@ int kueue_tas_host_update_nodes(kueue_tas_host* h, const char* nodes_json, int32
  * order] or null, "fillBackEvals": n}. */
 int kueue_tas_host_preemption_search(kueue_tas_host* h, const char* podsets_json, const char* candidates_json,
                                      char** out_json);
+
+/* The preemption search of a whole cycle, binary in and out: per preemptor
+ * exactly kueue_tas_host_preemption_search (`minimal`'s prefix scan with
+ * workloadFits reduced to "no PodSet result carries a reason", then
+ * fillBackWorkloads), batched across the n preemptors.
+ *  ids:      the preemptors, compiled workloads (kueue_tas_host_compile);
+ *  target_deltas / target_off / n_targets: the preemptable workloads' usage,
+ *            the table kueue_tas_host_admit_block_targets takes (a record
+ *            whose leaf or column is not the snapshot's: KUEUE_TAS_EINVAL);
+ *  cand / cand_off: preemptor p's candidates cand[cand_off[p] ..
+ *            cand_off[p + 1]) (target indices) in candidate order;
+ *  prefix_fits[cand_off[p] + i]: prefix {0..i} of preemptor p fits;
+ *  first_fit[p]: its first fitting prefix, -1: none;
+ *  entry_target_off [n + 1] / entry_targets: preemptor p's targets as target
+ *            indices in the reference's final order (swap-delete), none
+ *            without a fitting prefix: with ids, what
+ *            kueue_tas_host_admit_block_targets takes as entry lists.
+ * One kueue_tas_removal_tables_build with a set per preemptor; every prefix
+ * of every preemptor (mask (2 << i) - 1) in ONE batch; fillBack in lock-step:
+ * the reference's loop index starts at firstFit - 1 and falls by one per
+ * step whatever the swap-delete does, so round r evaluates every preemptor
+ * with firstFit - 1 - r >= 0 under "its targets without targets[i]":
+ * max firstFit batches, not their sum.  A batch is one batched evaluation of
+ * the host layer: one device batch per PodSet-group pass of its workloads.
+ * With KUEUE_TAS_PS_ASSIGN, updateAssignmentForTAS (scheduler.go:759-783):
+ * one more batch evaluates the preemptors with targets under their final
+ * mask, one WithSimulateEmpty batch those without a fitting prefix or
+ * without candidates; the results are published as kueue_tas_host_run
+ * publishes them (kueue_tas_host_last_assignments: quads under the
+ * preemptors' ids, which must then be distinct; kueue_tas_host_last_results
+ * in the order of ids) until the next kueue_tas_host_run.
+ * A preemptor with more than 64 candidates or with more than
+ * KUEUE_TAS_REMOVAL_SET_CAP records takes the host path: its overlays are
+ * merged on the host from the binary records and ride in the same batches;
+ * KUEUE_TAS_PS_HOST_OVERLAYS forces that for every preemptor.  The snapshot,
+ * the host mirror, the compiled workloads and the column set are untouched.
+ * kueue_tas_host_last_search_stats: [0] evaluations, [1] batches, [2]
+ * fillBack rounds, [3] sets on the device path, [4] on the host path, [5]
+ * removal bytes uploaded, [6] assumed records expanded on the device, [7]
+ * the call's wall time in microseconds. */
+#define KUEUE_TAS_PS_ASSIGN 1u
+#define KUEUE_TAS_PS_HOST_OVERLAYS 2u
+int kueue_tas_host_preemption_search_batch(kueue_tas_host* h, const int32_t* ids, size_t n,
+                                           const kueue_tas_delta* target_deltas, const int64_t* target_off,
+                                           size_t n_targets, const int32_t* cand, const int64_t* cand_off, uint32_t flags,
+                                           uint8_t* prefix_fits, int32_t* first_fit, int64_t* entry_target_off,
+                                           int32_t* entry_targets);
+int kueue_tas_host_last_search_stats(kueue_tas_host* h, int64_t out[8]);
 
 /* Batched partial-admission search: PodSetReducer.Search
  * (pkg/scheduler/flavorassigner/podset_reducer.go:37-86, called from

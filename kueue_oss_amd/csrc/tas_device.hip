@@ -440,6 +440,21 @@ struct kueue_tas_ctx {
   HostBuf<uint8_t> h_read;
   hipEvent_t ev_digest[3] = {};  // before the launches, after them, after the D2H (kueue_tas_last_digest_ms)
   float digest_ms[2] = {0, 0};
+  // resident removal tables (kueue_tas_removal_tables_build): the build's one
+  // upload (target records | list entries | cand_off | set_off), the sets'
+  // sorted tables, and the host's copy of what sizes an evaluation's range
+  HostBuf<uint8_t> h_rt;
+  DevBuf<uint8_t> d_rt;
+  DevBuf<kueue_tas_assumed> d_rt_table;
+  hipEvent_t ev_rt = nullptr;  // the upload's end (h_rt is rewritten by the next build)
+  bool rt_built = false;
+  int64_t rt_snap_gen = -1;    // n_loads + n_splices at the build: a load or splice since makes the tables stale
+  size_t rt_set_off_at = 0;    // byte offset of set_off in d_rt
+  std::vector<int32_t> rt_cand_off, rt_set_off;  // [sets + 1]
+  std::vector<int32_t> rt_pos_kept;              // per list entry: its target's records with leaf >= 0
+  int64_t rt_stats[4] = {0, 0, 0, 0};            // kueue_tas_removal_stats
+  // the chunk's masked evaluations (eval_chunk): each request's job (-1: none) and range length
+  std::vector<int32_t> req_job, req_xlen;
 };
 
 // The leaf-row scatter kernels write repeated entries in no fixed order:
@@ -592,6 +607,7 @@ void kueue_tas_ctx_destroy(kueue_tas_ctx* c) {
   for (auto& e : c->evs)
     if (e) (void)hipEventDestroy(e);
   if (c->ev_deltas) (void)hipEventDestroy(c->ev_deltas);
+  if (c->ev_rt) (void)hipEventDestroy(c->ev_rt);
   for (auto& e : c->ev_digest)
     if (e) (void)hipEventDestroy(e);
   if (c->stream3) (void)hipStreamDestroy(c->stream3);
@@ -2252,6 +2268,9 @@ struct ChunkArgs {
   int32_t* res_counts;
   float* ms;
   float* stage_ms;
+  // kueue_tas_eval_batch_removals: the requests' removal sets and masks (null: no request has one)
+  const int32_t* rset = nullptr;
+  const uint64_t* rmask = nullptr;
 };
 
 // Byte offsets of the staging arena's segments (h_stage and d_stage alike).
@@ -2261,7 +2280,9 @@ struct ArenaOffsets {
   size_t moff, mem;  // class members in fill order (CSR)
   size_t top;        // rollup_top_kernel's level maxima (INT32_MIN) and per-class arrival counters (0)
   size_t sel;        // BestFit-side select slots' buffers
-  size_t fpos;       // last: the per-position fill records, uploaded up to the batch's nfill
+  size_t rjobs;      // the masked evaluations' RemovalJob records
+  size_t fpos;       // last uploaded: the per-position fill records, up to the batch's nfill
+  size_t xassumed;   // device only, addressed from `assumed`: the masked evaluations' expanded ranges
 };
 
 struct ChunkPlan {
@@ -2280,6 +2301,8 @@ struct ChunkPlan {
   int nblk = 0;            // leaf partials per eval (one per 64-leaf wave)
   int lfc_cur = 0;         // the half of the LFC chunk tables this chunk uses
   size_t res_bytes = 0, res_off_stats = 0, stats_len = 0;  // d_res / h_res: out[n] | stats
+  int njobs = 0;           // masked evaluations (removal_expand_kernel's grid)
+  int64_t nexpanded = 0;   // assumed records of their ranges
 };
 
 // What the fill-path decision yields (enqueue_fill)
@@ -2321,9 +2344,27 @@ struct ClassKeys {
   size_t taint_table_len;
   int32_t P;  // taint profiles
   int L;      // levels
+  // masked evaluations: the record's assumed range is its expanded range on the
+  // device; the signature is the request's own records plus (set, mask)
+  const DevEval* hev;
+  const int32_t* job_of;  // null: the chunk has none
+  const RemovalJob* jobs;
   ClassKeys(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPlan& p)
       : hterms(stage_terms(c, p)), assumed(a.assumed), aff(a.aff), aff_vals(a.aff_vals), taint_table(a.taint_table),
-        taint_table_len(a.taint_table_len), P(c->num_profiles), L(c->snap.L) {}
+        taint_table_len(a.taint_table_len), P(c->num_profiles), L(c->snap.L), hev(stage_evals(c, p)),
+        job_of(p.njobs ? c->req_job.data() : nullptr),
+        jobs(reinterpret_cast<const RemovalJob*>(c->h_stage.p + p.o.rjobs)) {}
+
+  struct Overlay {
+    int32_t begin, end;  // the request's own records
+    int32_t set;         // -1: no removal
+    uint64_t mask;
+  };
+  Overlay overlay(const DevEval& e) const {
+    const int32_t j = job_of ? job_of[&e - hev] : -1;
+    if (j < 0) return {e.assumed_begin, e.assumed_end, -1, 0};
+    return {jobs[j].own_begin, jobs[j].own_end, jobs[j].set, jobs[j].mask};
+  }
 
   const int32_t* taint_row(const DevEval& e) const {
     return (taint_table && size_t(e.taint_table) + size_t(P) <= taint_table_len) ? taint_table + e.taint_table
@@ -2343,9 +2384,14 @@ struct ClassKeys {
       add(uint64_t(uint32_t(t.col)));
       add(uint64_t(t.val));
     }
-    for (int a = e.assumed_begin; a < e.assumed_end; a++) {
+    const Overlay ov = overlay(e);
+    for (int a = ov.begin; a < ov.end; a++) {
       add(uint64_t(uint32_t(assumed[a].leaf)) | (uint64_t(uint32_t(assumed[a].col)) << 32));
       add(uint64_t(assumed[a].value));
+    }
+    if (ov.set >= 0) {
+      add(0x5e7u | (uint64_t(uint32_t(ov.set)) << 32));
+      add(ov.mask);
     }
     return h;
   }
@@ -2384,10 +2430,12 @@ struct ClassKeys {
   // base signature: what the leaf's remaining capacity depends on (a fill chunk shares it)
   bool same_base(const DevEval& x, const DevEval& y) const {
     if ((x.flags ^ y.flags) & (KUEUE_TAS_F_LEADER | KUEUE_TAS_F_SIMULATE_EMPTY)) return false;
-    if (x.assumed_end - x.assumed_begin != y.assumed_end - y.assumed_begin) return false;
-    for (int a = 0; a < x.assumed_end - x.assumed_begin; a++) {
-      const kueue_tas_assumed& p = assumed[x.assumed_begin + a];
-      const kueue_tas_assumed& q = assumed[y.assumed_begin + a];
+    const Overlay ox = overlay(x), oy = overlay(y);
+    if (ox.set != oy.set || ox.mask != oy.mask) return false;
+    if (ox.end - ox.begin != oy.end - oy.begin) return false;
+    for (int a = 0; a < ox.end - ox.begin; a++) {
+      const kueue_tas_assumed& p = assumed[ox.begin + a];
+      const kueue_tas_assumed& q = assumed[oy.begin + a];
       if (p.leaf != q.leaf || p.col != q.col || p.value != q.value) return false;
     }
     return true;
@@ -2455,6 +2503,14 @@ static int validate_requests(kueue_tas_ctx* c, const ChunkArgs& a) {
   chunk_maxt.assign(std::max<size_t>(nparts, 1), 1);
   std::vector<std::pair<size_t, std::string>>& errs = c->req_errs;  // per part: (first bad request, message)
   errs.assign(std::max<size_t>(nparts, 1), {SIZE_MAX, std::string()});
+  std::vector<int32_t>& xlen = c->req_xlen;  // masked evaluations: the expanded range's length, else -1
+  int32_t nsets = 0;
+  if (a.rset) {
+    if (!c->rt_built) return fail(c, KUEUE_TAS_EINVAL, "no removal tables");
+    if (c->rt_snap_gen != c->n_loads + c->n_splices) return fail(c, KUEUE_TAS_EINVAL, "removal tables are stale");
+    nsets = int32_t(c->rt_set_off.size()) - 1;
+    xlen.assign(n, -1);
+  }
   auto validate = [&](size_t i, std::string* msg) -> bool {
     const auto& r = *reqs[i];
     if (r.num_req < 0 || r.num_req > KUEUE_TAS_MAX_COLS || r.num_leader_req < 0 || r.num_leader_req > KUEUE_TAS_MAX_COLS)
@@ -2497,6 +2553,20 @@ static int validate_requests(kueue_tas_ctx* c, const ChunkArgs& a) {
     if ((r.flags & KUEUE_TAS_F_DOMAIN) &&
         (r.domain_begin < 0 || r.domain_end < r.domain_begin || r.domain_end > s.N))
       return *msg = "required domain leaf range", false;
+    if (a.rset) {  // the removal's range: the request's own records plus the masked positions' records
+      xlen[i] = -1;
+      const int32_t set = a.rset[i];
+      const uint64_t mask = a.rmask[i];
+      if (set < -1 || set >= nsets) return *msg = "removal set out of range", false;
+      if (set >= 0 && mask) {
+        const int32_t c0 = c->rt_cand_off[size_t(set)], nc = c->rt_cand_off[size_t(set) + 1] - c0;
+        if (nc < 64 && (mask >> nc)) return *msg = "removal mask beyond the set's candidates", false;
+        int64_t len = int64_t(r.assumed_end) - r.assumed_begin;
+        for (uint64_t m = mask; m; m &= m - 1) len += c->rt_pos_kept[size_t(c0 + __builtin_ctzll(m))];
+        if (len > INT32_MAX) return *msg = "removal range too long", false;
+        xlen[i] = int32_t(len);
+      }
+    }
     return true;
   };
   pool.run_static(n, [&](size_t i0, size_t i1) {
@@ -2542,9 +2612,41 @@ static int layout_stage(kueue_tas_ctx* c, const ChunkArgs& a, ChunkPlan& p) {
   o.moff = seg((n + 1) * 4), o.mem = seg(n * 4);
   o.top = seg(n * (kMaxLevels + 1) * 4);
   o.sel = seg(n * sizeof(SelSlot));
+  // masked evaluations: a job each, and its range of the device's assumed
+  // records behind everything uploaded (the host only knows its length)
+  p.njobs = 0;
+  p.nexpanded = 0;
+  if (a.rset) {
+    c->req_job.assign(n, -1);
+    for (size_t i = 0; i < n; i++)
+      if (c->req_xlen[i] >= 0) {
+        c->req_job[i] = p.njobs++;
+        p.nexpanded += c->req_xlen[i];
+      }
+  }
+  o.rjobs = seg(size_t(p.njobs) * sizeof(RemovalJob));
   o.fpos = seg(n * sizeof(FillPos));
-  HIPCHK(c, c->h_stage.ensure(stage_bytes));
+  const size_t host_bytes = stage_bytes;
+  o.xassumed = seg(size_t(p.nexpanded) * sizeof(kueue_tas_assumed));
+  if ((o.xassumed - o.assumed) / sizeof(kueue_tas_assumed) + size_t(p.nexpanded) > size_t(INT32_MAX))
+    return fail(c, KUEUE_TAS_EOVERFLOW, "removal ranges exceed the assumed records' index");
+  HIPCHK(c, c->h_stage.ensure(host_bytes));
   HIPCHK(c, c->d_stage.ensure(stage_bytes));
+  if (p.njobs) {
+    RemovalJob* jobs = reinterpret_cast<RemovalJob*>(c->h_stage.p + o.rjobs);
+    int64_t at = int64_t((o.xassumed - o.assumed) / sizeof(kueue_tas_assumed));
+    for (size_t i = 0; i < n; i++) {
+      if (c->req_job[i] < 0) continue;
+      RemovalJob& jb = jobs[c->req_job[i]];
+      jb.mask = a.rmask[i];
+      jb.set = a.rset[i];
+      jb.own_begin = a.reqs[i]->assumed_begin;
+      jb.own_end = a.reqs[i]->assumed_end;
+      jb.out_begin = int32_t(at);
+      jb.out_end = int32_t(at += c->req_xlen[i]);
+      jb.pad = 0;
+    }
+  }
   const size_t nparts = ktas_pool::HostPool::get().parts();
   c->req_sig_hash.resize(n);   // signature hash per request
   c->req_cls_hash.resize(n);   // signature x mask hash per request
@@ -2598,6 +2700,10 @@ static int compile_requests(kueue_tas_ctx* c, const ChunkArgs& a, const ChunkPla
       e.taint_table = r.taint_table;
       e.assumed_begin = r.assumed_begin;
       e.assumed_end = r.assumed_end;
+      if (p.njobs && c->req_job[i] >= 0) {  // the expanded range (removal_expand_kernel writes it)
+        e.assumed_begin = keys.jobs[c->req_job[i]].out_begin;
+        e.assumed_end = keys.jobs[c->req_job[i]].out_end;
+      }
       e.aff_begin = r.affinity_begin;
       e.aff_end = r.affinity_end;
       e.dom_begin = (r.flags & KUEUE_TAS_F_DOMAIN) ? r.domain_begin : -1;
@@ -3335,6 +3441,16 @@ static int upload_and_describe(kueue_tas_ctx* c, const ChunkArgs& a, const Chunk
   b.fill_chunks = reinterpret_cast<const int32_t*>(ds + o.fchunks);
   b.fill_run = reinterpret_cast<const int32_t*>(ds + o.frun);
   b.fill_pos = reinterpret_cast<const FillPos*>(ds + o.fpos);
+  // the masked evaluations' assumed ranges, expanded behind the upload and
+  // before enqueue_fill records the event both fill streams start from
+  if (p.njobs) {
+    hipLaunchKernelGGL(removal_expand_kernel, dim3(unsigned(p.njobs)), dim3(kRemovalThreads), 0, c->stream,
+                       reinterpret_cast<const RemovalJob*>(ds + o.rjobs),
+                       reinterpret_cast<const int32_t*>(c->d_rt.p + c->rt_set_off_at), c->d_rt_table.p,
+                       reinterpret_cast<kueue_tas_assumed*>(ds + o.assumed));
+    HIPCHK(c, hipGetLastError());
+    c->rt_stats[3] += p.nexpanded;
+  }
   return KUEUE_TAS_OK;
 }
 
@@ -3962,6 +4078,14 @@ int kueue_tas_eval_batch(kueue_tas_ctx* c, const kueue_tas_eval_req* reqs, size_
                                    entries, entries_capacity, taint_counts, res_counts);
 }
 
+static int eval_batch_impl(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, size_t n,
+                           const int32_t* taint_table, size_t taint_table_len, int32_t num_taints,
+                           const kueue_tas_assumed* assumed, size_t num_assumed,
+                           const kueue_tas_affinity_req* affinity, size_t num_affinity,
+                           const int32_t* affinity_values, size_t num_affinity_values, kueue_tas_eval_out* out,
+                           int64_t* entry_offsets, int32_t* entries, size_t entries_capacity, int32_t* taint_counts,
+                           int32_t* res_counts, const int32_t* removal_set, const uint64_t* removal_mask);
+
 int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, size_t n,
                               const int32_t* taint_table, size_t taint_table_len, int32_t num_taints,
                               const kueue_tas_assumed* assumed, size_t num_assumed,
@@ -3969,6 +4093,36 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* c, const kueue_tas_eval_req* const*
                               const int32_t* affinity_values, size_t num_affinity_values, kueue_tas_eval_out* out,
                               int64_t* entry_offsets, int32_t* entries, size_t entries_capacity, int32_t* taint_counts,
                               int32_t* res_counts) {
+  return eval_batch_impl(c, reqs, n, taint_table, taint_table_len, num_taints, assumed, num_assumed, affinity,
+                         num_affinity, affinity_values, num_affinity_values, out, entry_offsets, entries,
+                         entries_capacity, taint_counts, res_counts, nullptr, nullptr);
+}
+
+int kueue_tas_eval_batch_removals(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, size_t n,
+                                  const int32_t* taint_table, size_t taint_table_len, int32_t num_taints,
+                                  const kueue_tas_assumed* assumed, size_t num_assumed,
+                                  const kueue_tas_affinity_req* affinity, size_t num_affinity,
+                                  const int32_t* affinity_values, size_t num_affinity_values, kueue_tas_eval_out* out,
+                                  int64_t* entry_offsets, int32_t* entries, size_t entries_capacity,
+                                  int32_t* taint_counts, int32_t* res_counts, const int32_t* removal_set,
+                                  const uint64_t* removal_mask) {
+  if (!c) return KUEUE_TAS_EINVAL;
+  bool any = false;  // no set or no masked position anywhere: the plain batch
+  if (removal_set && removal_mask)
+    for (size_t i = 0; i < n && !any; i++) any = removal_set[i] != -1 && removal_mask[i] != 0;
+  return eval_batch_impl(c, reqs, n, taint_table, taint_table_len, num_taints, assumed, num_assumed, affinity,
+                         num_affinity, affinity_values, num_affinity_values, out, entry_offsets, entries,
+                         entries_capacity, taint_counts, res_counts, any ? removal_set : nullptr,
+                         any ? removal_mask : nullptr);
+}
+
+static int eval_batch_impl(kueue_tas_ctx* c, const kueue_tas_eval_req* const* reqs, size_t n,
+                           const int32_t* taint_table, size_t taint_table_len, int32_t num_taints,
+                           const kueue_tas_assumed* assumed, size_t num_assumed,
+                           const kueue_tas_affinity_req* affinity, size_t num_affinity,
+                           const int32_t* affinity_values, size_t num_affinity_values, kueue_tas_eval_out* out,
+                           int64_t* entry_offsets, int32_t* entries, size_t entries_capacity, int32_t* taint_counts,
+                           int32_t* res_counts, const int32_t* removal_set, const uint64_t* removal_mask) {
   std::lock_guard<std::mutex> select_snap_lock(select_snap_mu);
   if (!c) return KUEUE_TAS_EINVAL;
   if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
@@ -4000,6 +4154,8 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* c, const kueue_tas_eval_req* const*
     a.offsets = off.data();
     a.taint_counts = taint_counts ? taint_counts + i0 * size_t(std::max(num_taints, 0)) : nullptr;
     a.res_counts = res_counts ? res_counts + i0 * size_t(c->snap.R) : nullptr;
+    a.rset = removal_set ? removal_set + i0 : nullptr;
+    a.rmask = removal_set ? removal_mask + i0 : nullptr;
     const size_t keep = c->ent_used;
     auto rewind = [&] {  // what a chunk that re-runs recorded for the batch
       c->ent_used = keep;
@@ -4045,6 +4201,111 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* c, const kueue_tas_eval_req* const*
   entry_offsets[n] = total;
   if (size_t(total) > entries_capacity) return fail(c, KUEUE_TAS_EOVERFLOW, "entries buffer too small");
   return kueue_tas_fetch_entries(c, entries, entries_capacity);
+}
+
+// ---- resident removal tables: validation and the positions' record counts on
+// the host (they size every evaluation's range without a synchronisation),
+// one upload, one removal_table_kernel launch (a workgroup per set). ----
+int kueue_tas_removal_tables_build(kueue_tas_ctx* c, const kueue_tas_delta* target_deltas, const int64_t* target_off,
+                                   size_t n_targets, const int32_t* cand, const int64_t* cand_off, size_t n_sets) {
+  if (!c) return KUEUE_TAS_EINVAL;
+  if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
+  if ((n_targets && !target_off) || (n_sets && !cand_off)) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+  if (n_targets >= size_t(INT32_MAX) || n_sets >= size_t(INT32_MAX)) return fail(c, KUEUE_TAS_EINVAL, "too many targets or sets");
+  const int32_t N = c->snap.N, R = c->snap.R;
+  if (n_targets && target_off[0] != 0) return fail(c, KUEUE_TAS_EINVAL, "target offsets do not start at 0");
+  for (size_t t = 0; t < n_targets; t++)
+    if (target_off[t + 1] < target_off[t]) return fail(c, KUEUE_TAS_EINVAL, "target offsets not monotone");
+  const int64_t nrec = n_targets ? target_off[n_targets] : 0;
+  if (nrec > INT32_MAX / 2 || (nrec && !target_deltas)) return fail(c, KUEUE_TAS_EINVAL, "target records");
+  std::vector<int32_t> kept(n_targets, 0);  // per target: records with leaf >= 0
+  for (size_t t = 0; t < n_targets; t++)
+    for (int64_t k = target_off[t]; k < target_off[t + 1]; k++) {
+      const kueue_tas_delta& x = target_deltas[k];
+      if (x.leaf < -1 || x.leaf >= N || x.col < 0 || x.col >= R || x.col > kRemovalColMask)
+        return fail(c, KUEUE_TAS_EINVAL, "target record out of range");
+      kept[t] += x.leaf >= 0;
+    }
+  if (n_sets && cand_off[0] != 0) return fail(c, KUEUE_TAS_EINVAL, "candidate offsets do not start at 0");
+  for (size_t s = 0; s < n_sets; s++) {
+    if (cand_off[s + 1] < cand_off[s]) return fail(c, KUEUE_TAS_EINVAL, "candidate offsets not monotone");
+    if (cand_off[s + 1] - cand_off[s] > KUEUE_TAS_REMOVAL_MAX_CANDIDATES)
+      return fail(c, KUEUE_TAS_EINVAL, "more than 64 candidates in a removal set");
+  }
+  const int64_t nent = n_sets ? cand_off[n_sets] : 0;
+  if (nent && !cand) return fail(c, KUEUE_TAS_EINVAL, "null argument");
+  std::vector<int32_t> set_off(n_sets + 1, 0), coff(n_sets + 1, 0), pos_kept(size_t(nent), 0);
+  for (size_t s = 0; s < n_sets; s++) {
+    int64_t raw = 0, kp = 0;
+    for (int64_t e = cand_off[s]; e < cand_off[s + 1]; e++) {
+      if (cand[e] < 0 || size_t(cand[e]) >= n_targets) return fail(c, KUEUE_TAS_EINVAL, "removal candidate out of range");
+      raw += target_off[cand[e] + 1] - target_off[cand[e]];
+      kp += pos_kept[size_t(e)] = kept[size_t(cand[e])];
+    }
+    if (raw > KUEUE_TAS_REMOVAL_SET_CAP) return fail(c, KUEUE_TAS_EOVERFLOW, "removal set above the record cap");
+    coff[s + 1] = int32_t(cand_off[s + 1]);
+    if (int64_t(set_off[s]) + kp > INT32_MAX) return fail(c, KUEUE_TAS_EOVERFLOW, "removal tables too large");
+    set_off[s + 1] = int32_t(set_off[s] + kp);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  // the upload: target records | list entries | cand_off | set_off
+  auto al = [](size_t b) { return (b + 15) / 16 * 16; };
+  const size_t o_ent = al(size_t(nrec) * sizeof(kueue_tas_delta)), o_coff = o_ent + al(size_t(nent) * 4);
+  const size_t o_soff = o_coff + al((n_sets + 1) * 4), bytes = o_soff + (n_sets + 1) * 4;
+  if (c->ev_rt) HIPCHK(c, hipEventSynchronize(c->ev_rt));
+  else HIPCHK(c, hipEventCreateWithFlags(&c->ev_rt, hipEventDisableTiming));
+  c->rt_built = false;  // (valid input: the resident tables are being replaced)
+  HIPCHK(c, c->h_rt.reserve(bytes));
+  HIPCHK(c, c->d_rt.reserve(bytes));
+  HIPCHK(c, c->d_rt_table.reserve(size_t(set_off[n_sets])));
+  kueue_tas_delta* h_rec = reinterpret_cast<kueue_tas_delta*>(c->h_rt.p);
+  int32_t* h_ent = reinterpret_cast<int32_t*>(c->h_rt.p + o_ent);
+  if (nrec) memcpy(h_rec, target_deltas, size_t(nrec) * sizeof(kueue_tas_delta));
+  for (size_t t = 0; t < n_targets; t++)  // a target's first record carries its record count
+    if (target_off[t + 1] > target_off[t])
+      h_rec[target_off[t]].col |=
+          int32_t(std::min<int64_t>(target_off[t + 1] - target_off[t], KUEUE_TAS_REMOVAL_SET_CAP + 1) << kRemovalPosShift);
+  for (int64_t e = 0; e < nent; e++)
+    h_ent[e] = target_off[cand[e] + 1] > target_off[cand[e]] ? int32_t(target_off[cand[e]]) : -1;
+  memcpy(c->h_rt.p + o_coff, coff.data(), (n_sets + 1) * 4);
+  memcpy(c->h_rt.p + o_soff, set_off.data(), (n_sets + 1) * 4);
+  HIPCHK(c, hipMemcpyAsync(c->d_rt.p, c->h_rt.p, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_rt, c->stream));
+  if (n_sets) {
+    hipLaunchKernelGGL(removal_table_kernel, dim3(unsigned(n_sets)), dim3(kRemovalThreads), 0, c->stream,
+                       reinterpret_cast<const kueue_tas_delta*>(c->d_rt.p),
+                       reinterpret_cast<const int32_t*>(c->d_rt.p + o_ent),
+                       reinterpret_cast<const int32_t*>(c->d_rt.p + o_coff),
+                       reinterpret_cast<const int32_t*>(c->d_rt.p + o_soff), c->d_rt_table.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  c->rt_cand_off.swap(coff);
+  c->rt_set_off.swap(set_off);
+  c->rt_pos_kept.swap(pos_kept);
+  c->rt_set_off_at = o_soff;
+  c->rt_snap_gen = c->n_loads + c->n_splices;
+  c->rt_built = true;
+  c->rt_stats[0] = int64_t(n_sets);
+  c->rt_stats[1] = c->rt_set_off[n_sets];
+  c->rt_stats[2] = int64_t(bytes);
+  c->rt_stats[3] = 0;
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_removal_tables_clear(kueue_tas_ctx* c) {
+  if (!c) return KUEUE_TAS_EINVAL;
+  c->rt_built = false;
+  c->rt_cand_off.clear();
+  c->rt_set_off.clear();
+  c->rt_pos_kept.clear();
+  for (auto& v : c->rt_stats) v = 0;
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_removal_stats(kueue_tas_ctx* c, int64_t out[4]) {
+  if (!c || !out) return KUEUE_TAS_EINVAL;
+  for (int k = 0; k < 4; k++) out[k] = c->rt_stats[k];
+  return KUEUE_TAS_OK;
 }
 
 int kueue_tas_last_counters(kueue_tas_ctx* c, size_t i, int32_t* out, size_t cap) {

@@ -2885,7 +2885,12 @@ struct PassTables {
   std::vector<int32_t> aff_vals;
   BatchList batch;
   BatchList early;  // groups that failed host-side validation: reported, not evaluated
+  // per request, when the run names removal sets (kueue_tas_eval_batch_removals): the set (-1: none) and mask
+  std::vector<int32_t> rset;
+  std::vector<uint64_t> rmask;
   void clear() {    // keeps capacity
+    rset.clear();
+    rmask.clear();
     reqs.clear();
     taint.clear();
     assumed.clear();
@@ -3035,6 +3040,10 @@ struct Evaluator {
       }
       q.assumed_end = int32_t(as.size());
       t.batch.emplace_back(w, &g);
+      if (rm_set) {  // the device expands the workload's removal behind the group's own records
+        t.rset.push_back((*rm_set)[w]);
+        t.rmask.push_back((*rm_mask)[w]);
+      }
     }
   }
 
@@ -3230,10 +3239,27 @@ struct Evaluator {
       for (size_t k = 0; k < m; k++) balReq.push_back(*pt.reqs[again[c0 + k]]);
       balOuts.resize(m);
       balOffs.resize(m + 1);
-      int rc = kueue_tas_eval_batch(s.ctx, balReq.data(), m, pt.taint.data(), pt.taint.size(),
-                                    int32_t(s.taintStrings.size()), pt.assumed.data(), pt.assumed.size(), pt.aff.data(),
-                                    pt.aff.size(), pt.aff_vals.data(), pt.aff_vals.size(), balOuts.data(),
-                                    balOffs.data(), nullptr, 0, nullptr, nullptr);
+      int rc;
+      if (pt.rset.empty()) {
+        rc = kueue_tas_eval_batch(s.ctx, balReq.data(), m, pt.taint.data(), pt.taint.size(),
+                                  int32_t(s.taintStrings.size()), pt.assumed.data(), pt.assumed.size(), pt.aff.data(),
+                                  pt.aff.size(), pt.aff_vals.data(), pt.aff_vals.size(), balOuts.data(), balOffs.data(),
+                                  nullptr, 0, nullptr, nullptr);
+      } else {  // the requests' removal sets go with them
+        std::vector<const kueue_tas_eval_req*> ptrs(m);
+        std::vector<int32_t> rs(m);
+        std::vector<uint64_t> rm(m);
+        for (size_t k = 0; k < m; k++) {
+          ptrs[k] = &balReq[k];
+          rs[k] = pt.rset[again[c0 + k]];
+          rm[k] = pt.rmask[again[c0 + k]];
+        }
+        rc = kueue_tas_eval_batch_removals(s.ctx, ptrs.data(), m, pt.taint.data(), pt.taint.size(),
+                                           int32_t(s.taintStrings.size()), pt.assumed.data(), pt.assumed.size(),
+                                           pt.aff.data(), pt.aff.size(), pt.aff_vals.data(), pt.aff_vals.size(),
+                                           balOuts.data(), balOffs.data(), nullptr, 0, nullptr, nullptr, rs.data(),
+                                           rm.data());
+      }
       for (size_t k = 0; k < m && rc == 0; k++) rc = place(again[c0 + k], k);
       if (rc) {
         snap->err = std::string("balanced placement: ") + kueue_tas_last_error(s.ctx);
@@ -3249,6 +3275,11 @@ struct Evaluator {
   // (SimulateUsageRemoval).
   using Overlay = std::vector<kueue_tas_assumed>;
   const std::vector<Overlay>* base = nullptr;
+  // per-workload removal set and mask of the context's resident removal tables
+  // (kueue_tas_removal_tables_build), expanded on the device; set with a
+  // `base` (possibly of empty overlays): a workload uses one or the other
+  const std::vector<int32_t>* rm_set = nullptr;
+  const std::vector<uint64_t>* rm_mask = nullptr;
 
   // ---- the stages of run(), in its order ----
   void reset_run(RunState& st) {
@@ -3339,11 +3370,13 @@ struct Evaluator {
     res_counts.resize(n * st.R);
     const bool packed = (snap->cfg.flags & KUEUE_TAS_CFG_PACKED_ENTRIES) != 0;
     if (packed && entries.size() < 2 * 64 * n) entries.resize(2 * 64 * n);
-    int rc = kueue_tas_eval_batch_ptrs(snap->ctx, t.reqs.data(), n, t.taint.data(), t.taint.size(), int32_t(st.T),
-                                       t.assumed.data(), t.assumed.size(), t.aff.data(), t.aff.size(),
-                                       t.aff_vals.data(), t.aff_vals.size(), outs.data(), offsets.data(),
-                                       packed ? entries.data() : nullptr, packed ? entries.size() / 2 : 0,
-                                       taint_counts.data(), res_counts.data());
+    int rc = kueue_tas_eval_batch_removals(snap->ctx, t.reqs.data(), n, t.taint.data(), t.taint.size(), int32_t(st.T),
+                                           t.assumed.data(), t.assumed.size(), t.aff.data(), t.aff.size(),
+                                           t.aff_vals.data(), t.aff_vals.size(), outs.data(), offsets.data(),
+                                           packed ? entries.data() : nullptr, packed ? entries.size() / 2 : 0,
+                                           taint_counts.data(), res_counts.data(),
+                                           t.rset.empty() ? nullptr : t.rset.data(),
+                                           t.rset.empty() ? nullptr : t.rmask.data());
     if (rc == KUEUE_TAS_EOVERFLOW && packed) {
       entries.resize(size_t(offsets[n]) * 2 + 2);
       rc = kueue_tas_fetch_entries(snap->ctx, entries.data(), entries.size() / 2);
@@ -3821,6 +3854,9 @@ struct kueue_tas_host {
   uint64_t compiled_gen = 0;  // bumped when the compiled workload set is replaced
   std::unique_ptr<Evaluator> ev;
   std::vector<std::vector<PodSetResult>> last;
+  // with KUEUE_TAS_PS_ASSIGN: last[i] belongs to compiled workload last_ids[i] (empty: to active()[i])
+  std::vector<int32_t> last_ids;
+  int64_t search_stats[8] = {};  // kueue_tas_host_last_search_stats
   RunDiag diag;  // of the last kueue_tas_host_run (kept when ev is reset)
   uint64_t compiled_cols = 0;  // FlavorSnapshot::col_gen the compiled workloads were compiled against
   // this rank's shard of the compiled workloads (indices into `compiled`)
@@ -4551,6 +4587,7 @@ static int rebuild(kueue_tas_host* h, const kjson::Node& node_events) {
   h->snap = std::move(ns);
   h->ev.reset();
   h->last.clear();
+  h->last_ids.clear();
   h->recompile_all();
   return h->snap->upload();
 }
@@ -4617,6 +4654,7 @@ int kueue_tas_host_update_nodes(kueue_tas_host* h, const char* nodes_json, int32
         h->snap->spliced = false;
         h->ev.reset();
         h->last.clear();
+        h->last_ids.clear();
       }
       um[6] = now_ms() - t4;
       rc = h->snap->push_liveness(liveChanged);
@@ -4795,6 +4833,244 @@ int kueue_tas_host_preemption_search(kueue_tas_host* h, const char* podsets_json
   }
 }
 
+// The preemption search of a whole cycle (kueue_tas_host_preemption_search_batch):
+// per preemptor exactly preemption_search above — `minimal`'s prefix scan, then
+// fillBackWorkloads — batched across the preemptors.  One removal set per
+// preemptor (kueue_tas_removal_tables_build) and an evaluation names a mask
+// over its candidates: every prefix of every preemptor in one batch, the
+// fillBack steps in lock-step rounds (the reference's index falls by one per
+// step whatever the swap-delete does, so round r holds every preemptor with
+// firstFit - 1 - r >= 0), then the final assignments (updateAssignmentForTAS,
+// scheduler.go:759-783).  A preemptor on the host path (more than 64
+// candidates, a set above the device's record cap, KUEUE_TAS_PS_HOST_OVERLAYS)
+// takes part in the same batches with its overlay merged here from the binary
+// records, as FlavorSnapshot::removal forms it.  Every evaluation is a copy of
+// the compiled workload's groups: the evaluator's builders write the batch
+// tables' offsets into the groups' records, and one workload appears many
+// times in a batch.
+static int preemption_search_batch(kueue_tas_host* h, const int32_t* ids, size_t n, const kueue_tas_delta* tdeltas,
+                                   const int64_t* toff, size_t n_targets, const int32_t* cand, const int64_t* coff,
+                                   uint32_t flags, uint8_t* prefix_fits, int32_t* first_fit, int64_t* entry_target_off,
+                                   int32_t* entry_targets) {
+  FlavorSnapshot& s = *h->snap;
+  const double t0 = now_ms();
+  int64_t* stats = h->search_stats;
+  for (int k = 0; k < 8; k++) stats[k] = 0;
+  auto bad = [&](const char* msg) {
+    s.err = msg;
+    return KUEUE_TAS_EINVAL;
+  };
+  if ((n && (!ids || !coff || !first_fit || !entry_target_off)) || (n_targets && !toff)) return bad("null argument");
+  for (size_t p = 0; p < n; p++)
+    if (ids[p] < 0 || size_t(ids[p]) >= h->compiled.size()) return bad("preemptor is not a compiled workload");
+  if (n && coff[0] != 0) return bad("candidate offsets do not start at 0");
+  for (size_t p = 0; p < n; p++)
+    if (coff[p + 1] < coff[p]) return bad("candidate offsets not monotone");
+  const int64_t nent = n ? coff[n] : 0;
+  if (nent && (!cand || !prefix_fits || !entry_targets)) return bad("null argument");
+  if (n_targets && toff[0] != 0) return bad("target offsets do not start at 0");
+  for (size_t t = 0; t < n_targets; t++)
+    if (toff[t + 1] < toff[t]) return bad("target offsets not monotone");
+  for (int64_t e = 0; e < nent; e++)
+    if (cand[e] < 0 || size_t(cand[e]) >= n_targets) return bad("candidate out of range");
+  if (h->compiled_cols != s.col_gen) h->recompile_all();  // (as kueue_tas_host_run)
+  int rc = s.upload();
+  if (rc) return rc;
+  const int64_t nrec = n_targets ? toff[n_targets] : 0;
+  if (nrec && !tdeltas) return bad("null argument");
+  for (int64_t k = 0; k < nrec; k++)
+    if (tdeltas[k].leaf < -1 || tdeltas[k].leaf >= s.N() || tdeltas[k].col < 0 || size_t(tdeltas[k].col) >= s.cols.size())
+      return bad("target record: leaf or column is not the snapshot's");
+
+  using Overlay = Evaluator::Overlay;
+  struct Pre {
+    bool dev = false;
+    long first = -1;
+    std::vector<int32_t> targets;  // candidate positions, the reference's order
+  };
+  std::vector<Pre> pre(n);
+  // the device's sets: a preemptor on the host path gets an empty one
+  std::vector<int32_t> scand;
+  std::vector<int64_t> soff(n + 1, 0);
+  for (size_t p = 0; p < n; p++) {
+    const int64_t k = coff[p + 1] - coff[p];
+    int64_t raw = 0;
+    for (int64_t e = coff[p]; e < coff[p + 1]; e++) raw += toff[cand[e] + 1] - toff[cand[e]];
+    pre[p].dev = !(flags & KUEUE_TAS_PS_HOST_OVERLAYS) && k <= KUEUE_TAS_REMOVAL_MAX_CANDIDATES &&
+                 raw <= KUEUE_TAS_REMOVAL_SET_CAP;
+    if (pre[p].dev) scand.insert(scand.end(), cand + coff[p], cand + coff[p + 1]);
+    soff[p + 1] = int64_t(scand.size());
+    stats[pre[p].dev ? 3 : 4]++;
+  }
+  if (stats[3]) {
+    rc = kueue_tas_removal_tables_build(s.ctx, tdeltas, toff, n_targets, scand.data(), soff.data(), n);
+    if (rc) {
+      s.err = std::string("removal tables: ") + kueue_tas_last_error(s.ctx);
+      return rc;
+    }
+    int64_t rs[4];
+    kueue_tas_removal_stats(s.ctx, rs);
+    stats[5] = rs[2];
+  }
+  // host path: the overlay of the selected candidate positions of preemptor p
+  auto overlay_of = [&](size_t p, const std::vector<int32_t>& positions) {
+    std::map<std::pair<int32_t, int32_t>, int64_t> o;
+    for (int32_t q : positions) {
+      const int32_t t = cand[coff[p] + q];
+      for (int64_t k = toff[t]; k < toff[t + 1]; k++) {
+        const kueue_tas_delta& d = tdeltas[k];
+        if (d.leaf < 0 || s.leafDead[size_t(d.leaf)]) continue;
+        int64_t& slot = o[{d.leaf, d.col}];
+        slot = sub64(slot, d.delta);
+      }
+    }
+    Overlay r;
+    r.reserve(o.size());
+    for (auto& kv : o) r.push_back({kv.first.first, kv.first.second, kv.second});
+    return r;
+  };
+  auto mask_of = [](const std::vector<int32_t>& positions) {
+    uint64_t m = 0;
+    for (int32_t q : positions) m |= 1ull << q;
+    return m;
+  };
+  struct Spec {
+    size_t p;
+    std::vector<int32_t> positions;  // the candidates removed
+  };
+  auto fits_all = [](const std::vector<PodSetResult>& rs) {
+    for (auto& r : rs)
+      if (!r.reason.empty()) return false;  // TASAssignmentsResult.Failure() (:384-391)
+    return true;
+  };
+  // one batch: every spec a copy of its preemptor's compiled groups
+  std::vector<std::vector<PodSetResult>> results;
+  auto evaluate = [&](const std::vector<Spec>& specs, bool simulateEmpty) -> int {
+    std::vector<Workload> wls(specs.size());
+    std::vector<Overlay> base(specs.size());
+    std::vector<int32_t> rset(specs.size(), -1);
+    std::vector<uint64_t> rmask(specs.size(), 0);
+    for (size_t i = 0; i < specs.size(); i++) {
+      const size_t p = specs[i].p;
+      wls[i].groups = h->compiled[size_t(ids[p])].groups;
+      if (simulateEmpty)
+        for (auto& g : wls[i].groups) g.req.flags |= KUEUE_TAS_F_SIMULATE_EMPTY;
+      if (pre[p].dev) {
+        rset[i] = int32_t(p);
+        rmask[i] = mask_of(specs[i].positions);
+      } else {
+        base[i] = overlay_of(p, specs[i].positions);
+      }
+    }
+    Evaluator ev{&s};
+    ev.rm_set = stats[3] ? &rset : nullptr;
+    ev.rm_mask = stats[3] ? &rmask : nullptr;
+    results.clear();
+    const int rc2 = ev.run(wls, false, &results, /*precompiled=*/true, &base);
+    if (rc2) return rc2;
+    for (auto& rs : results)  // (the views die with the next batch, the groups' names with wls)
+      for (auto& r : rs) r.materialize();
+    stats[0] += int64_t(specs.size());
+    stats[1]++;
+    return 0;
+  };
+
+  // every prefix of every preemptor: one batch
+  {
+    std::vector<Spec> specs;
+    for (size_t p = 0; p < n; p++)
+      for (int64_t i = 0; i < coff[p + 1] - coff[p]; i++) {
+        Spec sp{p, {}};
+        for (int64_t q = 0; q <= i; q++) sp.positions.push_back(int32_t(q));
+        specs.push_back(std::move(sp));
+      }
+    if (!specs.empty() && (rc = evaluate(specs, false))) return rc;
+    for (size_t i = 0; i < specs.size(); i++) {
+      const size_t p = specs[i].p;
+      const bool f = fits_all(results[i]);
+      prefix_fits[coff[p] + int64_t(specs[i].positions.size()) - 1] = f ? 1 : 0;
+      if (f && pre[p].first < 0) pre[p].first = long(specs[i].positions.size()) - 1;
+    }
+  }
+  long rounds = 0;
+  for (size_t p = 0; p < n; p++) {
+    first_fit[p] = int32_t(pre[p].first);
+    for (long q = 0; q <= pre[p].first; q++) pre[p].targets.push_back(int32_t(q));
+    rounds = std::max(rounds, pre[p].first);
+  }
+  // fillBackWorkloads (:330-345) in lock-step: round r is step i = firstFit - 1 - r
+  for (long r = 0; r < rounds; r++) {
+    std::vector<Spec> specs;
+    for (size_t p = 0; p < n; p++) {
+      const long i = pre[p].first - 1 - r;
+      if (i < 0) continue;
+      Spec sp{p, {}};
+      for (size_t j = 0; j < pre[p].targets.size(); j++)
+        if (long(j) != i) sp.positions.push_back(pre[p].targets[j]);
+      specs.push_back(std::move(sp));
+    }
+    if ((rc = evaluate(specs, false))) return rc;
+    stats[2]++;
+    for (size_t k = 0; k < specs.size(); k++) {
+      Pre& P = pre[specs[k].p];
+      const long i = P.first - 1 - r;
+      if (fits_all(results[k])) {
+        P.targets[size_t(i)] = P.targets.back();
+        P.targets.pop_back();
+      }
+    }
+  }
+  int64_t at = 0;
+  for (size_t p = 0; p < n; p++) {
+    entry_target_off[p] = at;
+    for (int32_t q : pre[p].targets) entry_targets[at++] = cand[coff[p] + q];
+  }
+  if (n) entry_target_off[n] = at;
+  if (flags & KUEUE_TAS_PS_ASSIGN) {
+    std::vector<std::vector<PodSetResult>> last(n);
+    for (int empty = 0; empty < 2; empty++) {  // with targets: their removal; without: the empty cluster
+      std::vector<Spec> specs;
+      for (size_t p = 0; p < n; p++)
+        if ((pre[p].first < 0) == (empty != 0)) specs.push_back({p, pre[p].targets});
+      if (specs.empty()) continue;
+      if ((rc = evaluate(specs, empty != 0))) return rc;
+      for (size_t k = 0; k < specs.size(); k++) last[specs[k].p] = std::move(results[k]);
+    }
+    h->last = std::move(last);
+    h->last_ids.assign(ids, ids + n);
+  }
+  if (stats[3]) {
+    int64_t rs[4];
+    kueue_tas_removal_stats(s.ctx, rs);
+    stats[6] = rs[3];
+  }
+  stats[7] = int64_t((now_ms() - t0) * 1000.0);
+  return 0;
+}
+
+int kueue_tas_host_preemption_search_batch(kueue_tas_host* h, const int32_t* ids, size_t n,
+                                           const kueue_tas_delta* target_deltas, const int64_t* target_off,
+                                           size_t n_targets, const int32_t* cand, const int64_t* cand_off, uint32_t flags,
+                                           uint8_t* prefix_fits, int32_t* first_fit, int64_t* entry_target_off,
+                                           int32_t* entry_targets) {
+  if (!h || !h->snap || !h->err.empty()) return KUEUE_TAS_EINVAL;
+  try {
+    const int rc = preemption_search_batch(h, ids, n, target_deltas, target_off, n_targets, cand, cand_off, flags,
+                                           prefix_fits, first_fit, entry_target_off, entry_targets);
+    if (rc) h->err = h->snap->err;
+    return rc;
+  } catch (const std::exception& e) {
+    h->err = e.what();
+    return KUEUE_TAS_EINVAL;
+  }
+}
+
+int kueue_tas_host_last_search_stats(kueue_tas_host* h, int64_t out[8]) {
+  if (!h || !out) return KUEUE_TAS_EINVAL;
+  for (int k = 0; k < 8; k++) out[k] = h->search_stats[k];
+  return 0;
+}
+
 // Batched partial-admission search: PodSetReducer.Search
 // (pkg/scheduler/flavorassigner/podset_reducer.go:37-86, driven by
 // Scheduler.getInitialAssignments, scheduler.go:720-739) with the fits closure
@@ -4945,6 +5221,7 @@ int kueue_tas_host_compile(kueue_tas_host* h, const char* workloads_json) {
     h->shard_ids.clear();
     h->shard.clear();
     h->compiled.assign(doc["workloads"].items.size(), Workload{});
+    h->last_ids.clear();
     h->compiled_gen++;
     for (size_t i = 0; i < h->compiled.size(); i++) {
       h->compiled[i].podsets = parse_podsets(doc["workloads"].items[i]);
@@ -4980,6 +5257,7 @@ int kueue_tas_host_run(kueue_tas_host* h, uint32_t flags, uint64_t* result_hash)
   if (!h->ev) h->ev = std::make_unique<Evaluator>(Evaluator{h->snap.get()});
   Evaluator& ev = *h->ev;
   std::vector<std::vector<PodSetResult>>& results = h->last;
+  h->last_ids.clear();
   const bool compile = (flags & KUEUE_TAS_RUN_COMPILE) != 0;
   int rc = ev.run(h->active(), false, &results, /*precompiled=*/!compile, nullptr, /*regroup=*/compile);
   if (rc) {
@@ -5183,6 +5461,7 @@ int kueue_tas_host_set_shard(kueue_tas_host* h, const int32_t* ids, size_t n) {
     }
     h->ev.reset();
     h->last.clear();
+    h->last_ids.clear();
     return 0;
   } catch (const std::exception& e) {
     h->err = e.what();
@@ -5201,8 +5480,10 @@ int kueue_tas_host_last_assignments(kueue_tas_host* h, int32_t* buf, size_t cap,
   *len = need;
   if (need > cap || (need && !buf)) return KUEUE_TAS_EOVERFLOW;
   size_t o = 0;
-  for (size_t i = 0; i < h->last.size() && i < wls.size(); i++) {
-    const int32_t g = h->shard_ids.empty() ? int32_t(i) : h->shard_ids[i];
+  const bool by_id = !h->last_ids.empty();  // a preemption search's final assignments
+  for (size_t i = 0; i < h->last.size() && i < (by_id ? h->last_ids.size() : wls.size()); i++) {
+    const int32_t g = by_id ? h->last_ids[i] : h->shard_ids.empty() ? int32_t(i) : h->shard_ids[i];
+    const Workload& wl = by_id ? h->compiled[size_t(g)] : wls[i];
     bool fail = false;
     int32_t nd = 0;
     for (auto& r : h->last[i]) {
@@ -5217,7 +5498,7 @@ int kueue_tas_host_last_assignments(kueue_tas_host* h, int32_t* buf, size_t cap,
     o += 4;
     for (auto& r : h->last[i]) {
       int32_t p = 0;
-      while (size_t(p) < wls[i].podsets.size() && wls[i].podsets[size_t(p)].name != r.name) p++;
+      while (size_t(p) < wl.podsets.size() && wl.podsets[size_t(p)].name != r.name) p++;
       for (auto& d : r.domains) {
         buf[o] = g;
         buf[o + 1] = p;

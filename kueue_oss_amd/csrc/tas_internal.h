@@ -275,5 +275,29 @@ struct DevBatch {
                            // (level_max_kernel; rows of class reps only), null: not computed
 };
 
+// ---- removal sets (kueue_tas_removal_tables_build / kueue_tas_eval_batch_removals) ----
+// A set's resident table: its candidates' delta records with leaf >= 0 as
+// assumed records (leaf, col | position << kRemovalPosShift, -delta), sorted by
+// leaf.  The uploaded target records carry their target's record count in
+// the first record's col (count << kRemovalPosShift): a list entry is then one
+// word, the target's first record (-1: a target without records).
+constexpr int kRemovalThreads = 256;                       // both kernels' workgroup
+constexpr int kRemovalSetCap = KUEUE_TAS_REMOVAL_SET_CAP;  // records a workgroup sorts in LDS
+constexpr int kRemovalExpandTile = kRemovalThreads;        // table records removal_expand_kernel compacts per step
+constexpr int kRemovalPosShift = 8;
+constexpr int kRemovalColMask = (1 << kRemovalPosShift) - 1;
+
+// One masked evaluation of a chunk (removal_expand_kernel, one workgroup each):
+// the set's table compacted by `mask` over the candidates' positions and
+// merged by leaf with the request's own assumed records [own_begin, own_end)
+// into [out_begin, out_end); all four index DevBatch::assumed.
+struct RemovalJob {
+  uint64_t mask;
+  int32_t set;
+  int32_t own_begin, own_end;
+  int32_t out_begin, out_end;
+  int32_t pad;
+};
+
 }  // namespace ktas
 #endif  // KTAS_INTERNAL_HOST_ONLY

@@ -7309,4 +7309,185 @@ __global__ void read_leaves_kernel(DevSnap s, const uint64_t* tags, const int32_
   for (int k = 0; k < s.K; k++) o_lab[int64_t(t) * s.K + k] = s.label_values ? s.label_values[int64_t(k) * s.N + leaf] : 0;
 }
 
+// ---- removal sets (kueue_tas_removal_tables_build, kueue_tas_eval_batch_removals) ----
+// FlavorSnapshot::removal on the device: a masked subset of a set's candidates
+// as assumed records (leaf, col, -delta).  The fills sum every assumed record
+// of a leaf that matches a column, so duplicates of a (leaf, col) stay as
+// they are: the records only have to be in leaf order.
+
+// removal_table_kernel: one workgroup per set.  The set's records, candidate
+// after candidate (position q = the q-th entry of the set's list), get the key
+// (leaf, gathered index) — leaf -1 as the largest leaf, so the dropped records
+// sort behind the `kept` ones the table stores — and a bitonic sort in LDS
+// puts them in leaf order, a leaf's records in candidate order.
+//  recs:     the uploaded target records (first record of a target: col |
+//            count << kRemovalPosShift)
+//  ent:      per list entry the target's first record, -1 for none
+//  cand_off: [sets + 1] the sets' list entries
+//  set_off:  [sets + 1] the sets' tables (records with leaf >= 0)
+// The host checked: <= 64 entries and <= kRemovalSetCap records per set.
+__global__ __launch_bounds__(kRemovalThreads) void removal_table_kernel(const kueue_tas_delta* recs, const int32_t* ent,
+                                                                        const int32_t* cand_off, const int32_t* set_off,
+                                                                        kueue_tas_assumed* table) {
+  __shared__ uint64_t sh_key[kRemovalSetCap];
+  __shared__ int32_t sh_begin[kWave];
+  __shared__ int32_t sh_roff[kWave + 1];
+  const int set = blockIdx.x, tid = threadIdx.x;
+  const int c0 = cand_off[set], nc = min(cand_off[set + 1] - c0, kWave);
+  const int t0 = set_off[set], kept = set_off[set + 1] - t0;
+  if (tid < kWave) {
+    const int bg = tid < nc ? ent[c0 + tid] : -1;
+    sh_begin[tid] = bg;
+    sh_roff[tid + 1] = bg >= 0 ? int32_t(uint32_t(recs[bg].col) >> kRemovalPosShift) : 0;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int at = 0;
+    for (int q = 0; q < nc; q++) {
+      const int cnt = sh_roff[q + 1];
+      sh_roff[q] = at;
+      at += cnt;
+    }
+    sh_roff[nc] = at;
+  }
+  __syncthreads();
+  const int raw = min(sh_roff[nc], kRemovalSetCap);
+  int n2 = 1;
+  while (n2 < raw) n2 <<= 1;
+  // the position of gathered index g: the last q with roff[q] <= g (positions without records share an offset)
+  auto position = [&](int g) {
+    int lo = 0, hi = nc;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (sh_roff[mid + 1] <= g) lo = mid + 1;
+      else hi = mid;
+    }
+    return lo;
+  };
+  for (int g = tid; g < n2; g += kRemovalThreads) {
+    uint64_t key = ~0ull;
+    if (g < raw) {
+      const int q = position(g);
+      const int leaf = recs[sh_begin[q] + (g - sh_roff[q])].leaf;
+      key = (uint64_t(uint32_t(leaf < 0 ? INT32_MAX : leaf)) << 32) | uint32_t(g);
+    }
+    sh_key[g] = key;
+  }
+  __syncthreads();
+  for (int k = 2; k <= n2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += kRemovalThreads) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const uint64_t a = sh_key[i], b = sh_key[ixj];
+          if ((a > b) == ((i & k) == 0)) {
+            sh_key[i] = b;
+            sh_key[ixj] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  for (int g = tid; g < kept && g < raw; g += kRemovalThreads) {
+    const uint64_t key = sh_key[g];
+    const int idx = int(uint32_t(key));
+    const int q = position(idx);
+    const kueue_tas_delta r = recs[sh_begin[q] + (idx - sh_roff[q])];
+    if (r.leaf < 0) continue;  // (the host counted `kept` over leaf >= 0)
+    kueue_tas_assumed o;
+    o.leaf = r.leaf;
+    o.col = (r.col & kRemovalColMask) | (q << kRemovalPosShift);
+    o.value = int64_t(0ull - uint64_t(r.delta));
+    table[t0 + g] = o;
+  }
+}
+
+// removal_expand_kernel: one workgroup per masked evaluation (RemovalJob).
+// The set's table goes by in tiles of kRemovalExpandTile records: the records
+// of masked positions keep their order (wave ballots, a scan of the waves'
+// counts), and merge by leaf with the request's own assumed records — a kept
+// record lands behind the own records of its leaf and of lower leaves, an own
+// record behind the kept records of lower leaves — into the evaluation's
+// reserved range of the batch's assumed records.  Nothing outside
+// [out_begin, out_end) is written.
+__global__ __launch_bounds__(kRemovalThreads) void removal_expand_kernel(const RemovalJob* jobs, const int32_t* set_off,
+                                                                         const kueue_tas_assumed* table,
+                                                                         kueue_tas_assumed* assumed) {
+  __shared__ int32_t sh_excl[kRemovalExpandTile];
+  __shared__ int32_t sh_wave[kRemovalThreads / kWave];
+  const RemovalJob jb = jobs[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  const int tn = set_off[jb.set + 1] - set_off[jb.set];
+  const kueue_tas_assumed* T = table + set_off[jb.set];
+  const kueue_tas_assumed* own = assumed + jb.own_begin;
+  const int own_n = jb.own_end - jb.own_begin;
+  kueue_tas_assumed* out = assumed + jb.out_begin;
+  const int cap = jb.out_end - jb.out_begin;
+  int base = 0;  // kept records of the tiles before
+  for (int ts = 0; ts < tn; ts += kRemovalExpandTile) {
+    const int t = ts + tid;
+    kueue_tas_assumed r;
+    r.leaf = 0, r.col = 0, r.value = 0;
+    bool keep = false;
+    if (t < tn) {
+      r = T[t];
+      keep = ((jb.mask >> ((uint32_t(r.col) >> kRemovalPosShift) & 63u)) & 1ull) != 0;
+    }
+    const uint64_t bal = __ballot(keep);
+    if (lane == 0) sh_wave[wv] = __popcll(bal);
+    __syncthreads();
+    int ex = __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+    for (int w = 0; w < kRemovalThreads / kWave; w++) {
+      const int v = sh_wave[w];
+      if (w < wv) ex += v;
+      total += v;
+    }
+    sh_excl[tid] = ex;
+    if (keep) {
+      int lo = 0, hi = own_n;  // own records with leaf <= r.leaf
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (own[mid].leaf <= r.leaf) lo = mid + 1;
+        else hi = mid;
+      }
+      const int pos = base + ex + lo;
+      if (pos < cap) {
+        r.col &= kRemovalColMask;
+        out[pos] = r;
+      }
+    }
+    __syncthreads();
+    // the own records whose first table record of an equal or higher leaf lies in this tile
+    const int te = min(ts + kRemovalExpandTile, tn);
+    for (int j = tid; j < own_n; j += kRemovalThreads) {
+      const kueue_tas_assumed o = own[j];
+      int lo = 0, hi = tn;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (T[mid].leaf < o.leaf) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo >= ts && lo < te) {
+        const int pos = j + base + sh_excl[lo - ts];
+        if (pos < cap) out[pos] = o;
+      }
+    }
+    base += total;
+    __syncthreads();
+  }
+  for (int j = tid; j < own_n; j += kRemovalThreads) {  // own records behind every table record
+    const kueue_tas_assumed o = own[j];
+    int lo = 0, hi = tn;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (T[mid].leaf < o.leaf) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo == tn) {
+      const int pos = j + base;
+      if (pos < cap) out[pos] = o;
+    }
+  }
+}
+
 }  // namespace ktas

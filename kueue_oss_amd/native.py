@@ -76,6 +76,8 @@ EXPORTED_SYMBOLS = [
     "kueue_tas_host_usage_deltas", "kueue_tas_host_last_admit_block_path", "kueue_tas_host_column_generation",
     "kueue_tas_snapshot_digest", "kueue_tas_snapshot_read_leaves", "kueue_tas_last_digest_ms",
     "kueue_tas_host_snapshot_digest", "kueue_tas_host_verify_device",
+    "kueue_tas_removal_tables_build", "kueue_tas_removal_tables_clear", "kueue_tas_eval_batch_removals",
+    "kueue_tas_removal_stats", "kueue_tas_host_preemption_search_batch", "kueue_tas_host_last_search_stats",
 ]
 
 # the Makefile's SRC_HASH inputs, in order
@@ -254,6 +256,13 @@ def _bind(lib):
     for name in ("kueue_tas_host_snapshot_digest", "kueue_tas_host_verify_device"):
         getattr(lib, name).argtypes = [c.c_void_p, c.POINTER(c.c_void_p)]
         getattr(lib, name).restype = c.c_int
+    if hasattr(lib, "kueue_tas_host_preemption_search_batch"):  # (builds of earlier commits lack them)
+        lib.kueue_tas_host_preemption_search_batch.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p,
+                                                               c.c_size_t, c.c_void_p, c.c_void_p, c.c_uint32,
+                                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+        lib.kueue_tas_host_preemption_search_batch.restype = c.c_int
+        lib.kueue_tas_host_last_search_stats.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
+        lib.kueue_tas_host_last_search_stats.restype = c.c_int
 
 
 def resource_quantity_string(name: str, value: int, lib=None) -> str:
@@ -664,6 +673,53 @@ class TASFlavorSnapshot:
         np.cumsum([len(p) for p in parts], out=off[1:])
         flat = np.concatenate(parts) if parts else np.zeros(0, dtype=DELTA_DTYPE)
         return np.ascontiguousarray(flat, dtype=DELTA_DTYPE), off
+
+    SEARCH_STATS = ("evaluations", "batches", "fillBackRounds", "deviceSets", "hostSets", "removalBytesUploaded",
+                    "recordsExpanded", "wallUs")
+
+    def preemption_search_batch(self, ids, workloads, candidates, assign: bool = False,
+                                host_overlays: bool = False) -> dict:
+        """The preemption search of a cycle (kueue_tas_host_preemption_search_batch):
+        ``ids`` the preempting heads (compiled workloads, compile()),
+        ``workloads`` the preemptable workloads as for admit_block (DELTA_DTYPE
+        arrays or usage-record lists), ``candidates[p]`` the workload indices
+        of preemptor ``ids[p]`` in candidate order.  Returns {"prefixFits":
+        [[bool] per preemptor], "firstFit": int32 array (-1: no prefix fits),
+        "targets": {id: [workload indices]} of the preemptors with a fitting
+        prefix, in the reference's final order, "stats": {...}}; ``targets``
+        goes unchanged into admit_block(..., workloads=workloads,
+        targets=targets) and sharding.admit_round.  With ``assign`` the final
+        assignments (updateAssignmentForTAS: under the targets' removal, or
+        WithSimulateEmpty without a fitting prefix) are what last_assignments()
+        and last_results() return, under ``ids``.  ``host_overlays`` expands
+        every removal on the host (the path of preemptors with more than 64
+        candidates) instead of on the device."""
+        import numpy as np
+        td, toff = self._target_table(workloads)
+        pid = np.ascontiguousarray(ids, dtype=np.int32)
+        if len(candidates) != pid.size:
+            raise ValueError("one candidate list per preemptor")
+        coff = np.zeros(pid.size + 1, dtype=np.int64)
+        np.cumsum([len(cs) for cs in candidates], out=coff[1:])
+        cand = np.array([int(t) for cs in candidates for t in cs], dtype=np.int32)
+        pf = np.zeros(max(cand.size, 1), dtype=np.uint8)
+        first = np.zeros(max(pid.size, 1), dtype=np.int32)
+        eoff = np.zeros(pid.size + 1, dtype=np.int64)
+        etg = np.zeros(max(cand.size, 1), dtype=np.int32)
+        rc = self._lib.kueue_tas_host_preemption_search_batch(
+            self._h, pid.ctypes.data, pid.size, td.ctypes.data, toff.ctypes.data, len(toff) - 1, cand.ctypes.data,
+            coff.ctypes.data, (1 if assign else 0) | (2 if host_overlays else 0), pf.ctypes.data, first.ctypes.data,
+            eoff.ctypes.data, etg.ctypes.data)
+        if rc:
+            raise RuntimeError(f"kueue_tas_host_preemption_search_batch failed ({rc}): {self._err()}")
+        st = (ctypes.c_int64 * 8)()
+        self._lib.kueue_tas_host_last_search_stats(self._h, st)
+        first = first[: pid.size]
+        return {"prefixFits": [[bool(x) for x in pf[coff[p]: coff[p + 1]]] for p in range(pid.size)],
+                "firstFit": first,
+                "targets": {int(pid[p]): [int(t) for t in etg[eoff[p]: eoff[p + 1]]]
+                            for p in range(pid.size) if first[p] >= 0},
+                "stats": dict(zip(self.SEARCH_STATS, (int(x) for x in st)))}
 
     def last_admit_block_path(self):
         """Where the last admit_block admitted: "device" (from the block), "host"
