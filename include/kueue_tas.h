@@ -375,18 +375,37 @@ int kueue_tas_eval_batch_ptrs(kueue_tas_ctx* ctx, const kueue_tas_eval_req* cons
  * host uploads bytes linear in the table, never in the number of masks.  The
  * single-workgroup sort bounds a set: at most KUEUE_TAS_REMOVAL_SET_CAP records
  * (those with leaf -1 included) over its candidates.
+ * removal_tables_build_flags with KUEUE_TAS_RT_LARGE_SETS lifts that bound to
+ * KUEUE_TAS_REMOVAL_LARGE_SET_CAP records: a set above KUEUE_TAS_REMOVAL_SET_CAP
+ * is a large set.  All large sets of a build go through the same launches: a
+ * workgroup sorts each chunk of KUEUE_TAS_REMOVAL_SET_CAP records in LDS
+ * (removal_chunk_sort_kernel), ceil(log2(chunks of the largest set)) passes
+ * merge the sorted runs pairwise by rank between two key buffers
+ * (removal_merge_kernel), and the table is stored with, per segment of 4096
+ * table records, the record counts of every position before the segment
+ * (removal_store_kernel, removal_seg_prefix_kernel).  The table is the same
+ * object as a small set's; a masked evaluation of a large set is expanded by
+ * one workgroup per segment (removal_expand_seg_kernel).  The large cap keeps
+ * a target's record count inside the bits of the uploaded first record's
+ * column word and a set's table at 16 MiB.  Flags 0 is removal_tables_build.
  * Returns, with the previous tables unchanged: KUEUE_TAS_EINVAL for offsets
  * that are not monotone from 0, a target index outside [0, n_targets), more
  * than 64 candidates in a set, a record's leaf outside [-1, N) or column
- * outside [0, R); KUEUE_TAS_EOVERFLOW for a set above the record cap (the
- * caller expands that set's overlays on the host).
+ * outside [0, R), an unknown flag; KUEUE_TAS_EOVERFLOW for a set above the
+ * record cap, with KUEUE_TAS_RT_LARGE_SETS above the large cap (the caller
+ * expands that set's overlays on the host).
  * The tables stay until the next build, removal_tables_clear, or a load or
  * splice of the snapshot (leaf indices change): kueue_tas_eval_batch_removals
  * with a set then returns KUEUE_TAS_EINVAL ("removal tables are stale"). */
 #define KUEUE_TAS_REMOVAL_MAX_CANDIDATES 64
 #define KUEUE_TAS_REMOVAL_SET_CAP 4096
+#define KUEUE_TAS_REMOVAL_LARGE_SET_CAP (1 << 20) /* records per set, leaf -1 included */
+#define KUEUE_TAS_RT_LARGE_SETS 1u
 int kueue_tas_removal_tables_build(kueue_tas_ctx* ctx, const kueue_tas_delta* target_deltas, const int64_t* target_off,
                                    size_t n_targets, const int32_t* cand, const int64_t* cand_off, size_t n_sets);
+int kueue_tas_removal_tables_build_flags(kueue_tas_ctx* ctx, const kueue_tas_delta* target_deltas,
+                                         const int64_t* target_off, size_t n_targets, const int32_t* cand,
+                                         const int64_t* cand_off, size_t n_sets, uint32_t flags);
 int kueue_tas_removal_tables_clear(kueue_tas_ctx* ctx);
 /* kueue_tas_eval_batch_ptrs with a removal per request: removal_set[i] is a
  * set of the resident tables (-1: none) and removal_mask[i] the positions
@@ -407,6 +426,11 @@ int kueue_tas_eval_batch_removals(kueue_tas_ctx* ctx, const kueue_tas_eval_req* 
  * [1] table records resident, [2] bytes the build uploaded, [3] assumed
  * records expanded on the device since the build (summed over evaluations). */
 int kueue_tas_removal_stats(kueue_tas_ctx* ctx, int64_t out[4]);
+/* The large sets of the last build (they count in removal_stats too): [0]
+ * large sets resident, [1] their table records, [2] merge launches of the
+ * build, [3] expand workgroups launched for large sets since the build (one
+ * per evaluation and segment; a table without records is one segment). */
+int kueue_tas_removal_large_stats(kueue_tas_ctx* ctx, int64_t out[4]);
 
 /* Phase-1 counters of request i of the last kueue_tas_eval_batch (its
  * fillInCounts + fillInCountsHelper result, tas_flavor_snapshot.go:1568-1719):
@@ -846,9 +870,11 @@ int kueue_tas_host_preemption_search(kueue_tas_host* h, const char* podsets_json
  * preemptors' ids, which must then be distinct; kueue_tas_host_last_results
  * in the order of ids) until the next kueue_tas_host_run.
  * A preemptor with more than 64 candidates or with more than
- * KUEUE_TAS_REMOVAL_SET_CAP records takes the host path: its overlays are
- * merged on the host from the binary records and ride in the same batches;
- * KUEUE_TAS_PS_HOST_OVERLAYS forces that for every preemptor.  The snapshot,
+ * KUEUE_TAS_REMOVAL_LARGE_SET_CAP records takes the host path: its overlays
+ * are merged on the host from the binary records and ride in the same
+ * batches; KUEUE_TAS_PS_HOST_OVERLAYS forces that for every preemptor, and
+ * KUEUE_TAS_PS_SMALL_SETS_ONLY for those above KUEUE_TAS_REMOVAL_SET_CAP
+ * records (the tables are then built without large sets).  The snapshot,
  * the host mirror, the compiled workloads and the column set are untouched.
  * kueue_tas_host_last_search_stats: [0] evaluations, [1] batches, [2]
  * fillBack rounds, [3] sets on the device path, [4] on the host path, [5]
@@ -856,6 +882,7 @@ int kueue_tas_host_preemption_search(kueue_tas_host* h, const char* podsets_json
  * the call's wall time in microseconds. */
 #define KUEUE_TAS_PS_ASSIGN 1u
 #define KUEUE_TAS_PS_HOST_OVERLAYS 2u
+#define KUEUE_TAS_PS_SMALL_SETS_ONLY 4u
 int kueue_tas_host_preemption_search_batch(kueue_tas_host* h, const int32_t* ids, size_t n,
                                            const kueue_tas_delta* target_deltas, const int64_t* target_off,
                                            size_t n_targets, const int32_t* cand, const int64_t* cand_off, uint32_t flags,

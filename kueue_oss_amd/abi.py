@@ -196,6 +196,9 @@ def bind_device_layer(lib):
     lib.kueue_tas_removal_tables_build.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p,
                                                    c.c_void_p, c.c_size_t]
     lib.kueue_tas_removal_tables_build.restype = c.c_int
+    lib.kueue_tas_removal_tables_build_flags.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p,
+                                                         c.c_void_p, c.c_size_t, c.c_uint32]
+    lib.kueue_tas_removal_tables_build_flags.restype = c.c_int
     lib.kueue_tas_removal_tables_clear.argtypes = [c.c_void_p]
     lib.kueue_tas_removal_tables_clear.restype = c.c_int
     # (reqs: an array of pointers to the requests, as kueue_tas_eval_batch_ptrs takes them)
@@ -206,23 +209,33 @@ def bind_device_layer(lib):
     lib.kueue_tas_eval_batch_removals.restype = c.c_int
     lib.kueue_tas_removal_stats.argtypes = [c.c_void_p, P(c.c_int64)]
     lib.kueue_tas_removal_stats.restype = c.c_int
+    lib.kueue_tas_removal_large_stats.argtypes = [c.c_void_p, P(c.c_int64)]
+    lib.kueue_tas_removal_large_stats.restype = c.c_int
     return lib
 
 
 REMOVAL_MAX_CANDIDATES = 64  # KUEUE_TAS_REMOVAL_MAX_CANDIDATES
 REMOVAL_SET_CAP = 4096       # KUEUE_TAS_REMOVAL_SET_CAP: records one removal_table_kernel workgroup sorts
 REMOVAL_EXPAND_TILE = 256    # table records removal_expand_kernel compacts per step (tas_internal.h)
+REMOVAL_LARGE_SET_CAP = 1 << 20  # KUEUE_TAS_REMOVAL_LARGE_SET_CAP: records of a set built with RT_LARGE_SETS
+REMOVAL_EXPAND_SEGMENT = 4096    # table records per removal_expand_seg_kernel workgroup (tas_internal.h)
+RT_LARGE_SETS = 1                # KUEUE_TAS_RT_LARGE_SETS
 
 
-def removal_tables_build(lib, ctx, targets, sets):
+def removal_tables_build(lib, ctx, targets, sets, flags=0):
     """kueue_tas_removal_tables_build from Python lists: ``targets[t]`` the
     (leaf, col, delta) records of target t, ``sets[s]`` the target indices of
-    set s.  Returns the call's code."""
+    set s.  With ``flags`` (RT_LARGE_SETS) through
+    kueue_tas_removal_tables_build_flags.  Returns the call's code."""
     import numpy as np
     recs = np.array([r for t in targets for r in t], dtype=[("leaf", "<i4"), ("col", "<i4"), ("delta", "<i8")])
     toff = np.cumsum([0] + [len(t) for t in targets], dtype=np.int64)
     cand = np.array([x for s in sets for x in s], dtype=np.int32)
     coff = np.cumsum([0] + [len(s) for s in sets], dtype=np.int64)
+    if flags:
+        return lib.kueue_tas_removal_tables_build_flags(ctx, recs.ctypes.data if recs.size else None, toff.ctypes.data,
+                                                        len(targets), cand.ctypes.data if cand.size else None,
+                                                        coff.ctypes.data, len(sets), flags)
     return lib.kueue_tas_removal_tables_build(ctx, recs.ctypes.data if recs.size else None, toff.ctypes.data,
                                               len(targets), cand.ctypes.data if cand.size else None, coff.ctypes.data,
                                               len(sets))

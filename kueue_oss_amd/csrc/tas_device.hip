@@ -453,6 +453,12 @@ struct kueue_tas_ctx {
   std::vector<int32_t> rt_cand_off, rt_set_off;  // [sets + 1]
   std::vector<int32_t> rt_pos_kept;              // per list entry: its target's records with leaf >= 0
   int64_t rt_stats[4] = {0, 0, 0, 0};            // kueue_tas_removal_stats
+  // large sets (KUEUE_TAS_RT_LARGE_SETS), allocated by the first build that has one: the merge
+  // passes' two key buffers (a key per record of the large sets) and the segments' position prefixes
+  DevBuf<uint64_t> d_rt_keys[2];
+  DevBuf<int32_t> d_rt_seg_prefix;               // [segments of all large sets][64]
+  std::vector<int32_t> rt_large_seg_off;         // per set: its first row of d_rt_seg_prefix, -1: a small set
+  int64_t rt_large_stats[4] = {0, 0, 0, 0};      // kueue_tas_removal_large_stats
   // the chunk's masked evaluations (eval_chunk): each request's job (-1: none) and range length
   std::vector<int32_t> req_job, req_xlen;
 };
@@ -2281,6 +2287,7 @@ struct ArenaOffsets {
   size_t top;        // rollup_top_kernel's level maxima (INT32_MIN) and per-class arrival counters (0)
   size_t sel;        // BestFit-side select slots' buffers
   size_t rjobs;      // the masked evaluations' RemovalJob records
+  size_t rsegs;      // removal_expand_seg_kernel's blocks (int4 each; none without large sets' evaluations)
   size_t fpos;       // last uploaded: the per-position fill records, up to the batch's nfill
   size_t xassumed;   // device only, addressed from `assumed`: the masked evaluations' expanded ranges
 };
@@ -2301,7 +2308,9 @@ struct ChunkPlan {
   int nblk = 0;            // leaf partials per eval (one per 64-leaf wave)
   int lfc_cur = 0;         // the half of the LFC chunk tables this chunk uses
   size_t res_bytes = 0, res_off_stats = 0, stats_len = 0;  // d_res / h_res: out[n] | stats
-  int njobs = 0;           // masked evaluations (removal_expand_kernel's grid)
+  int njobs = 0;           // masked evaluations: first the small sets' (removal_expand_kernel's grid) ...
+  int nsmalljobs = 0;      // ... then the large sets', a workgroup per segment each
+  int nsegblocks = 0;      // removal_expand_seg_kernel's grid
   int64_t nexpanded = 0;   // assumed records of their ranges
 };
 
@@ -2614,17 +2623,34 @@ static int layout_stage(kueue_tas_ctx* c, const ChunkArgs& a, ChunkPlan& p) {
   o.sel = seg(n * sizeof(SelSlot));
   // masked evaluations: a job each, and its range of the device's assumed
   // records behind everything uploaded (the host only knows its length)
-  p.njobs = 0;
+  p.njobs = p.nsmalljobs = p.nsegblocks = 0;
   p.nexpanded = 0;
+  auto large_row = [&](size_t i) {  // request i's set is a large one: its first row of seg_prefix, else -1
+    return c->rt_large_seg_off.empty() ? -1 : c->rt_large_seg_off[size_t(a.rset[i])];
+  };
+  auto set_segments = [&](int32_t set) {
+    const int32_t kept = c->rt_set_off[size_t(set) + 1] - c->rt_set_off[size_t(set)];
+    return std::max(1, (kept + kRemovalExpandSegment - 1) / kRemovalExpandSegment);
+  };
   if (a.rset) {
     c->req_job.assign(n, -1);
+    int64_t nseg = 0;
+    int nlarge = 0;
     for (size_t i = 0; i < n; i++)
       if (c->req_xlen[i] >= 0) {
-        c->req_job[i] = p.njobs++;
+        if (large_row(i) >= 0) nlarge++, nseg += set_segments(a.rset[i]);
+        else c->req_job[i] = p.nsmalljobs++;
         p.nexpanded += c->req_xlen[i];
       }
+    p.njobs = p.nsmalljobs;
+    if (nlarge)
+      for (size_t i = 0; i < n; i++)
+        if (c->req_xlen[i] >= 0 && c->req_job[i] < 0) c->req_job[i] = p.njobs++;
+    if (nseg > INT32_MAX / 2) return fail(c, KUEUE_TAS_EOVERFLOW, "too many segments of large removal sets in a chunk");
+    p.nsegblocks = int(nseg);
   }
   o.rjobs = seg(size_t(p.njobs) * sizeof(RemovalJob));
+  o.rsegs = seg(size_t(p.nsegblocks) * sizeof(int4));
   o.fpos = seg(n * sizeof(FillPos));
   const size_t host_bytes = stage_bytes;
   o.xassumed = seg(size_t(p.nexpanded) * sizeof(kueue_tas_assumed));
@@ -2634,9 +2660,13 @@ static int layout_stage(kueue_tas_ctx* c, const ChunkArgs& a, ChunkPlan& p) {
   HIPCHK(c, c->d_stage.ensure(stage_bytes));
   if (p.njobs) {
     RemovalJob* jobs = reinterpret_cast<RemovalJob*>(c->h_stage.p + o.rjobs);
+    int4* segs = reinterpret_cast<int4*>(c->h_stage.p + o.rsegs);
     int64_t at = int64_t((o.xassumed - o.assumed) / sizeof(kueue_tas_assumed));
     for (size_t i = 0; i < n; i++) {
       if (c->req_job[i] < 0) continue;
+      if (c->req_job[i] >= p.nsmalljobs)  // a large set: (job, first table record, seg_prefix row, last) per segment
+        for (int32_t k = 0, ns = set_segments(a.rset[i]), row = large_row(i); k < ns; k++)
+          *segs++ = make_int4(c->req_job[i], k * kRemovalExpandSegment, row + k, k == ns - 1);
       RemovalJob& jb = jobs[c->req_job[i]];
       jb.mask = a.rmask[i];
       jb.set = a.rset[i];
@@ -3444,11 +3474,22 @@ static int upload_and_describe(kueue_tas_ctx* c, const ChunkArgs& a, const Chunk
   // the masked evaluations' assumed ranges, expanded behind the upload and
   // before enqueue_fill records the event both fill streams start from
   if (p.njobs) {
-    hipLaunchKernelGGL(removal_expand_kernel, dim3(unsigned(p.njobs)), dim3(kRemovalThreads), 0, c->stream,
-                       reinterpret_cast<const RemovalJob*>(ds + o.rjobs),
-                       reinterpret_cast<const int32_t*>(c->d_rt.p + c->rt_set_off_at), c->d_rt_table.p,
-                       reinterpret_cast<kueue_tas_assumed*>(ds + o.assumed));
-    HIPCHK(c, hipGetLastError());
+    if (p.nsmalljobs) {
+      hipLaunchKernelGGL(removal_expand_kernel, dim3(unsigned(p.nsmalljobs)), dim3(kRemovalThreads), 0, c->stream,
+                         reinterpret_cast<const RemovalJob*>(ds + o.rjobs),
+                         reinterpret_cast<const int32_t*>(c->d_rt.p + c->rt_set_off_at), c->d_rt_table.p,
+                         reinterpret_cast<kueue_tas_assumed*>(ds + o.assumed));
+      HIPCHK(c, hipGetLastError());
+    }
+    if (p.nsegblocks) {  // the large sets' evaluations: a workgroup per segment of the table
+      hipLaunchKernelGGL(removal_expand_seg_kernel, dim3(unsigned(p.nsegblocks)), dim3(kRemovalThreads), 0, c->stream,
+                         reinterpret_cast<const RemovalJob*>(ds + o.rjobs), reinterpret_cast<const int4*>(ds + o.rsegs),
+                         reinterpret_cast<const int32_t*>(c->d_rt.p + c->rt_set_off_at), c->d_rt_table.p,
+                         static_cast<const int32_t*>(c->d_rt_seg_prefix.p),
+                         reinterpret_cast<kueue_tas_assumed*>(ds + o.assumed));
+      HIPCHK(c, hipGetLastError());
+      c->rt_large_stats[3] += p.nsegblocks;
+    }
     c->rt_stats[3] += p.nexpanded;
   }
   return KUEUE_TAS_OK;
@@ -4205,11 +4246,22 @@ static int eval_batch_impl(kueue_tas_ctx* c, const kueue_tas_eval_req* const* re
 
 // ---- resident removal tables: validation and the positions' record counts on
 // the host (they size every evaluation's range without a synchronisation),
-// one upload, one removal_table_kernel launch (a workgroup per set). ----
+// one upload, one removal_table_kernel launch (a workgroup per set).  With
+// KUEUE_TAS_RT_LARGE_SETS the sets above kRemovalSetCap records go through the
+// large sets' launches behind it, all of them together: the host knows every
+// set's raw and kept counts, so it sizes the grids and the merge passes. ----
 int kueue_tas_removal_tables_build(kueue_tas_ctx* c, const kueue_tas_delta* target_deltas, const int64_t* target_off,
                                    size_t n_targets, const int32_t* cand, const int64_t* cand_off, size_t n_sets) {
+  return kueue_tas_removal_tables_build_flags(c, target_deltas, target_off, n_targets, cand, cand_off, n_sets, 0);
+}
+
+int kueue_tas_removal_tables_build_flags(kueue_tas_ctx* c, const kueue_tas_delta* target_deltas,
+                                         const int64_t* target_off, size_t n_targets, const int32_t* cand,
+                                         const int64_t* cand_off, size_t n_sets, uint32_t flags) {
   if (!c) return KUEUE_TAS_EINVAL;
   if (!c->loaded) return fail(c, KUEUE_TAS_ENOSNAPSHOT, "no snapshot loaded");
+  if (flags & ~KUEUE_TAS_RT_LARGE_SETS) return fail(c, KUEUE_TAS_EINVAL, "unknown removal table flags");
+  const int64_t set_cap = (flags & KUEUE_TAS_RT_LARGE_SETS) ? KUEUE_TAS_REMOVAL_LARGE_SET_CAP : KUEUE_TAS_REMOVAL_SET_CAP;
   if ((n_targets && !target_off) || (n_sets && !cand_off)) return fail(c, KUEUE_TAS_EINVAL, "null argument");
   if (n_targets >= size_t(INT32_MAX) || n_sets >= size_t(INT32_MAX)) return fail(c, KUEUE_TAS_EINVAL, "too many targets or sets");
   const int32_t N = c->snap.N, R = c->snap.R;
@@ -4235,6 +4287,9 @@ int kueue_tas_removal_tables_build(kueue_tas_ctx* c, const kueue_tas_delta* targ
   const int64_t nent = n_sets ? cand_off[n_sets] : 0;
   if (nent && !cand) return fail(c, KUEUE_TAS_EINVAL, "null argument");
   std::vector<int32_t> set_off(n_sets + 1, 0), coff(n_sets + 1, 0), pos_kept(size_t(nent), 0);
+  std::vector<RemovalLargeSet> large;  // the large sets, then the totals
+  std::vector<int32_t> large_seg_off;  // per set (filled with the first large set)
+  int64_t nkeys = 0, nchunks = 0, nsegs = 0, max_chunks = 0, large_kept = 0;
   for (size_t s = 0; s < n_sets; s++) {
     int64_t raw = 0, kp = 0;
     for (int64_t e = cand_off[s]; e < cand_off[s + 1]; e++) {
@@ -4242,33 +4297,55 @@ int kueue_tas_removal_tables_build(kueue_tas_ctx* c, const kueue_tas_delta* targ
       raw += target_off[cand[e] + 1] - target_off[cand[e]];
       kp += pos_kept[size_t(e)] = kept[size_t(cand[e])];
     }
-    if (raw > KUEUE_TAS_REMOVAL_SET_CAP) return fail(c, KUEUE_TAS_EOVERFLOW, "removal set above the record cap");
+    if (raw > set_cap) return fail(c, KUEUE_TAS_EOVERFLOW, "removal set above the record cap");
     coff[s + 1] = int32_t(cand_off[s + 1]);
     if (int64_t(set_off[s]) + kp > INT32_MAX) return fail(c, KUEUE_TAS_EOVERFLOW, "removal tables too large");
     set_off[s + 1] = int32_t(set_off[s] + kp);
+    if (raw > KUEUE_TAS_REMOVAL_SET_CAP) {  // a large set: a key per record, a sort per chunk, a prefix row per segment
+      if (large.empty()) large_seg_off.assign(n_sets, -1);
+      large.push_back({int32_t(s), int32_t(nkeys), int32_t(nchunks), int32_t(nsegs)});
+      large_seg_off[s] = int32_t(nsegs);
+      const int64_t chunks = (raw + kRemovalSetCap - 1) / kRemovalSetCap;
+      nkeys += raw;
+      nchunks += chunks;
+      nsegs += std::max<int64_t>(1, (kp + kRemovalExpandSegment - 1) / kRemovalExpandSegment);  // (no records: one segment)
+      max_chunks = std::max(max_chunks, chunks);
+      large_kept += kp;
+      if (nkeys > INT32_MAX / 2) return fail(c, KUEUE_TAS_EOVERFLOW, "removal tables too large");
+    }
   }
+  const size_t nl = large.size();
+  if (nl) large.push_back({-1, int32_t(nkeys), int32_t(nchunks), int32_t(nsegs)});
   HIPCHK(c, hipSetDevice(c->device));
   // the upload: target records | list entries | cand_off | set_off
   auto al = [](size_t b) { return (b + 15) / 16 * 16; };
   const size_t o_ent = al(size_t(nrec) * sizeof(kueue_tas_delta)), o_coff = o_ent + al(size_t(nent) * 4);
-  const size_t o_soff = o_coff + al((n_sets + 1) * 4), bytes = o_soff + (n_sets + 1) * 4;
+  const size_t o_soff = o_coff + al((n_sets + 1) * 4);
+  const size_t o_large = nl ? al(o_soff + (n_sets + 1) * 4) : 0;  // (a build without large sets: not a byte more)
+  const size_t bytes = nl ? o_large + large.size() * sizeof(RemovalLargeSet) : o_soff + (n_sets + 1) * 4;
   if (c->ev_rt) HIPCHK(c, hipEventSynchronize(c->ev_rt));
   else HIPCHK(c, hipEventCreateWithFlags(&c->ev_rt, hipEventDisableTiming));
   c->rt_built = false;  // (valid input: the resident tables are being replaced)
   HIPCHK(c, c->h_rt.reserve(bytes));
   HIPCHK(c, c->d_rt.reserve(bytes));
   HIPCHK(c, c->d_rt_table.reserve(size_t(set_off[n_sets])));
+  if (nl) {
+    HIPCHK(c, c->d_rt_keys[0].reserve(size_t(nkeys)));
+    HIPCHK(c, c->d_rt_keys[1].reserve(size_t(nkeys)));
+    HIPCHK(c, c->d_rt_seg_prefix.reserve(size_t(nsegs) * kWave));
+  }
   kueue_tas_delta* h_rec = reinterpret_cast<kueue_tas_delta*>(c->h_rt.p);
   int32_t* h_ent = reinterpret_cast<int32_t*>(c->h_rt.p + o_ent);
   if (nrec) memcpy(h_rec, target_deltas, size_t(nrec) * sizeof(kueue_tas_delta));
   for (size_t t = 0; t < n_targets; t++)  // a target's first record carries its record count
     if (target_off[t + 1] > target_off[t])
       h_rec[target_off[t]].col |=
-          int32_t(std::min<int64_t>(target_off[t + 1] - target_off[t], KUEUE_TAS_REMOVAL_SET_CAP + 1) << kRemovalPosShift);
+          int32_t(std::min<int64_t>(target_off[t + 1] - target_off[t], set_cap + 1) << kRemovalPosShift);
   for (int64_t e = 0; e < nent; e++)
     h_ent[e] = target_off[cand[e] + 1] > target_off[cand[e]] ? int32_t(target_off[cand[e]]) : -1;
   memcpy(c->h_rt.p + o_coff, coff.data(), (n_sets + 1) * 4);
   memcpy(c->h_rt.p + o_soff, set_off.data(), (n_sets + 1) * 4);
+  if (nl) memcpy(c->h_rt.p + o_large, large.data(), large.size() * sizeof(RemovalLargeSet));
   HIPCHK(c, hipMemcpyAsync(c->d_rt.p, c->h_rt.p, bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipEventRecord(c->ev_rt, c->stream));
   if (n_sets) {
@@ -4279,6 +4356,36 @@ int kueue_tas_removal_tables_build(kueue_tas_ctx* c, const kueue_tas_delta* targ
                        reinterpret_cast<const int32_t*>(c->d_rt.p + o_soff), c->d_rt_table.p);
     HIPCHK(c, hipGetLastError());
   }
+  int passes = 0;
+  if (nl) {  // chunk sort | merge passes | store | segment prefix, ordered by the stream alone
+    static_assert(kRemovalSetCap == 1 << 12, "removal_merge_kernel's first runs are the sorted chunks");
+    const kueue_tas_delta* d_rec = reinterpret_cast<const kueue_tas_delta*>(c->d_rt.p);
+    const int32_t* d_ent = reinterpret_cast<const int32_t*>(c->d_rt.p + o_ent);
+    const int32_t* d_coff = reinterpret_cast<const int32_t*>(c->d_rt.p + o_coff);
+    const RemovalLargeSet* d_large = reinterpret_cast<const RemovalLargeSet*>(c->d_rt.p + o_large);
+    hipLaunchKernelGGL(removal_chunk_sort_kernel, dim3(unsigned(nchunks)), dim3(kRemovalThreads), 0, c->stream, d_rec,
+                       d_ent, d_coff, d_large, int(nl), c->d_rt_keys[0].p);
+    HIPCHK(c, hipGetLastError());
+    while ((int64_t(1) << passes) < max_chunks) passes++;
+    for (int p = 0; p < passes; p++) {
+      hipLaunchKernelGGL(removal_merge_kernel, dim3(unsigned(nchunks)), dim3(kRemovalThreads), 0, c->stream, d_large,
+                         int(nl), static_cast<const uint64_t*>(c->d_rt_keys[p & 1].p), c->d_rt_keys[(p + 1) & 1].p,
+                         12 + p);
+      HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(removal_store_kernel, dim3(unsigned(nsegs)), dim3(kRemovalThreads), 0, c->stream, d_rec, d_ent,
+                       d_coff, reinterpret_cast<const int32_t*>(c->d_rt.p + o_soff), d_large, int(nl),
+                       static_cast<const uint64_t*>(c->d_rt_keys[passes & 1].p), c->d_rt_table.p, c->d_rt_seg_prefix.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(removal_seg_prefix_kernel, dim3(unsigned(nl)), dim3(kWave), 0, c->stream, d_large,
+                       c->d_rt_seg_prefix.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  c->rt_large_seg_off.swap(large_seg_off);
+  c->rt_large_stats[0] = int64_t(nl);
+  c->rt_large_stats[1] = large_kept;
+  c->rt_large_stats[2] = passes;
+  c->rt_large_stats[3] = 0;
   c->rt_cand_off.swap(coff);
   c->rt_set_off.swap(set_off);
   c->rt_pos_kept.swap(pos_kept);
@@ -4298,13 +4405,21 @@ int kueue_tas_removal_tables_clear(kueue_tas_ctx* c) {
   c->rt_cand_off.clear();
   c->rt_set_off.clear();
   c->rt_pos_kept.clear();
+  c->rt_large_seg_off.clear();
   for (auto& v : c->rt_stats) v = 0;
+  for (auto& v : c->rt_large_stats) v = 0;
   return KUEUE_TAS_OK;
 }
 
 int kueue_tas_removal_stats(kueue_tas_ctx* c, int64_t out[4]) {
   if (!c || !out) return KUEUE_TAS_EINVAL;
   for (int k = 0; k < 4; k++) out[k] = c->rt_stats[k];
+  return KUEUE_TAS_OK;
+}
+
+int kueue_tas_removal_large_stats(kueue_tas_ctx* c, int64_t out[4]) {
+  if (!c || !out) return KUEUE_TAS_EINVAL;
+  for (int k = 0; k < 4; k++) out[k] = c->rt_large_stats[k];
   return KUEUE_TAS_OK;
 }
 

@@ -4842,7 +4842,8 @@ int kueue_tas_host_preemption_search(kueue_tas_host* h, const char* podsets_json
 // step whatever the swap-delete does, so round r holds every preemptor with
 // firstFit - 1 - r >= 0), then the final assignments (updateAssignmentForTAS,
 // scheduler.go:759-783).  A preemptor on the host path (more than 64
-// candidates, a set above the device's record cap, KUEUE_TAS_PS_HOST_OVERLAYS)
+// candidates, a set above the device's record cap — the large sets' cap, with
+// KUEUE_TAS_PS_SMALL_SETS_ONLY the small one — or KUEUE_TAS_PS_HOST_OVERLAYS)
 // takes part in the same batches with its overlay merged here from the binary
 // records, as FlavorSnapshot::removal forms it.  Every evaluation is a copy of
 // the compiled workload's groups: the evaluator's builders write the batch
@@ -4892,18 +4893,20 @@ static int preemption_search_batch(kueue_tas_host* h, const int32_t* ids, size_t
   // the device's sets: a preemptor on the host path gets an empty one
   std::vector<int32_t> scand;
   std::vector<int64_t> soff(n + 1, 0);
+  // (KUEUE_TAS_PS_SMALL_SETS_ONLY: the tables are built without large sets, sets above the small cap merge here)
+  const uint32_t rt_flags = (flags & KUEUE_TAS_PS_SMALL_SETS_ONLY) ? 0u : KUEUE_TAS_RT_LARGE_SETS;
+  const int64_t set_cap = rt_flags ? KUEUE_TAS_REMOVAL_LARGE_SET_CAP : KUEUE_TAS_REMOVAL_SET_CAP;
   for (size_t p = 0; p < n; p++) {
     const int64_t k = coff[p + 1] - coff[p];
     int64_t raw = 0;
     for (int64_t e = coff[p]; e < coff[p + 1]; e++) raw += toff[cand[e] + 1] - toff[cand[e]];
-    pre[p].dev = !(flags & KUEUE_TAS_PS_HOST_OVERLAYS) && k <= KUEUE_TAS_REMOVAL_MAX_CANDIDATES &&
-                 raw <= KUEUE_TAS_REMOVAL_SET_CAP;
+    pre[p].dev = !(flags & KUEUE_TAS_PS_HOST_OVERLAYS) && k <= KUEUE_TAS_REMOVAL_MAX_CANDIDATES && raw <= set_cap;
     if (pre[p].dev) scand.insert(scand.end(), cand + coff[p], cand + coff[p + 1]);
     soff[p + 1] = int64_t(scand.size());
     stats[pre[p].dev ? 3 : 4]++;
   }
   if (stats[3]) {
-    rc = kueue_tas_removal_tables_build(s.ctx, tdeltas, toff, n_targets, scand.data(), soff.data(), n);
+    rc = kueue_tas_removal_tables_build_flags(s.ctx, tdeltas, toff, n_targets, scand.data(), soff.data(), n, rt_flags);
     if (rc) {
       s.err = std::string("removal tables: ") + kueue_tas_last_error(s.ctx);
       return rc;

@@ -286,6 +286,20 @@ constexpr int kRemovalSetCap = KUEUE_TAS_REMOVAL_SET_CAP;  // records a workgrou
 constexpr int kRemovalExpandTile = kRemovalThreads;        // table records removal_expand_kernel compacts per step
 constexpr int kRemovalPosShift = 8;
 constexpr int kRemovalColMask = (1 << kRemovalPosShift) - 1;
+// a large set's table is expanded by a workgroup per segment of this many records
+constexpr int kRemovalExpandSegment = 4096;
+static_assert(kRemovalExpandSegment % kRemovalExpandTile == 0, "a segment is whole tiles");
+static_assert(int64_t(KUEUE_TAS_REMOVAL_LARGE_SET_CAP) < (int64_t(1) << (31 - kRemovalPosShift)),
+              "a target's record count fits above kRemovalPosShift");
+
+// A large set (KUEUE_TAS_RT_LARGE_SETS: above kRemovalSetCap records) as its
+// kernels see it; the array has one more entry that holds the totals.
+struct RemovalLargeSet {
+  int32_t set;        // index among the build's sets
+  int32_t key_off;    // first key of the set in the key buffers (one key per record, leaf -1 included)
+  int32_t chunk_off;  // first kRemovalSetCap-record chunk (removal_chunk_sort_kernel's and removal_merge_kernel's block)
+  int32_t seg_off;    // first segment (removal_store_kernel's block, row of seg_prefix)
+};
 
 // One masked evaluation of a chunk (removal_expand_kernel, one workgroup each):
 // the set's table compacted by `mask` over the candidates' positions and

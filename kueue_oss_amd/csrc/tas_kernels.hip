@@ -7315,26 +7315,12 @@ __global__ void read_leaves_kernel(DevSnap s, const uint64_t* tags, const int32_
 // of a leaf that matches a column, so duplicates of a (leaf, col) stay as
 // they are: the records only have to be in leaf order.
 
-// removal_table_kernel: one workgroup per set.  The set's records, candidate
-// after candidate (position q = the q-th entry of the set's list), get the key
-// (leaf, gathered index) — leaf -1 as the largest leaf, so the dropped records
-// sort behind the `kept` ones the table stores — and a bitonic sort in LDS
-// puts them in leaf order, a leaf's records in candidate order.
-//  recs:     the uploaded target records (first record of a target: col |
-//            count << kRemovalPosShift)
-//  ent:      per list entry the target's first record, -1 for none
-//  cand_off: [sets + 1] the sets' list entries
-//  set_off:  [sets + 1] the sets' tables (records with leaf >= 0)
-// The host checked: <= 64 entries and <= kRemovalSetCap records per set.
-__global__ __launch_bounds__(kRemovalThreads) void removal_table_kernel(const kueue_tas_delta* recs, const int32_t* ent,
-                                                                        const int32_t* cand_off, const int32_t* set_off,
-                                                                        kueue_tas_assumed* table) {
-  __shared__ uint64_t sh_key[kRemovalSetCap];
-  __shared__ int32_t sh_begin[kWave];
-  __shared__ int32_t sh_roff[kWave + 1];
-  const int set = blockIdx.x, tid = threadIdx.x;
-  const int c0 = cand_off[set], nc = min(cand_off[set + 1] - c0, kWave);
-  const int t0 = set_off[set], kept = set_off[set + 1] - t0;
+// The three pieces removal_table_kernel and the large sets' kernels share.
+// removal_list_offsets: a set's list (c0, nc <= 64 entries) into sh_begin (each
+// entry's first record, -1: none) and sh_roff (the entries' gathered offsets,
+// sh_roff[nc] the set's record count).  Every thread of the workgroup calls it.
+__device__ __forceinline__ void removal_list_offsets(const kueue_tas_delta* recs, const int32_t* ent, int c0, int nc,
+                                                     int tid, int32_t* sh_begin, int32_t* sh_roff) {
   if (tid < kWave) {
     const int bg = tid < nc ? ent[c0 + tid] : -1;
     sh_begin[tid] = bg;
@@ -7351,29 +7337,25 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_table_kernel(const ku
     sh_roff[nc] = at;
   }
   __syncthreads();
-  const int raw = min(sh_roff[nc], kRemovalSetCap);
-  int n2 = 1;
-  while (n2 < raw) n2 <<= 1;
-  // the position of gathered index g: the last q with roff[q] <= g (positions without records share an offset)
-  auto position = [&](int g) {
-    int lo = 0, hi = nc;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (sh_roff[mid + 1] <= g) lo = mid + 1;
-      else hi = mid;
-    }
-    return lo;
-  };
-  for (int g = tid; g < n2; g += kRemovalThreads) {
-    uint64_t key = ~0ull;
-    if (g < raw) {
-      const int q = position(g);
-      const int leaf = recs[sh_begin[q] + (g - sh_roff[q])].leaf;
-      key = (uint64_t(uint32_t(leaf < 0 ? INT32_MAX : leaf)) << 32) | uint32_t(g);
-    }
-    sh_key[g] = key;
+}
+
+// the position of gathered index g: the last q with roff[q] <= g (positions without records share an offset)
+__device__ __forceinline__ int removal_position(const int32_t* sh_roff, int nc, int g) {
+  int lo = 0, hi = nc;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sh_roff[mid + 1] <= g) lo = mid + 1;
+    else hi = mid;
   }
-  __syncthreads();
+  return lo;
+}
+
+__device__ __forceinline__ uint64_t removal_key(int leaf, int g) {  // leaf -1 sorts last
+  return (uint64_t(uint32_t(leaf < 0 ? INT32_MAX : leaf)) << 32) | uint32_t(g);
+}
+
+// the bitonic network over n2 (a power of two <= kRemovalSetCap) keys in LDS, ascending
+__device__ __forceinline__ void removal_bitonic_sort(uint64_t* sh_key, int n2, int tid) {
   for (int k = 2; k <= n2; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int i = tid; i < n2; i += kRemovalThreads) {
@@ -7388,10 +7370,48 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_table_kernel(const ku
       }
       __syncthreads();
     }
+}
+
+// removal_table_kernel: one workgroup per set.  The set's records, candidate
+// after candidate (position q = the q-th entry of the set's list), get the key
+// (leaf, gathered index) — leaf -1 as the largest leaf, so the dropped records
+// sort behind the `kept` ones the table stores — and a bitonic sort in LDS
+// puts them in leaf order, a leaf's records in candidate order.
+//  recs:     the uploaded target records (first record of a target: col |
+//            count << kRemovalPosShift)
+//  ent:      per list entry the target's first record, -1 for none
+//  cand_off: [sets + 1] the sets' list entries
+//  set_off:  [sets + 1] the sets' tables (records with leaf >= 0)
+// The host checked: <= 64 entries per set.  A set above kRemovalSetCap records
+// is a large set (KUEUE_TAS_RT_LARGE_SETS): the kernels below build its table.
+__global__ __launch_bounds__(kRemovalThreads) void removal_table_kernel(const kueue_tas_delta* recs, const int32_t* ent,
+                                                                        const int32_t* cand_off, const int32_t* set_off,
+                                                                        kueue_tas_assumed* table) {
+  __shared__ uint64_t sh_key[kRemovalSetCap];
+  __shared__ int32_t sh_begin[kWave];
+  __shared__ int32_t sh_roff[kWave + 1];
+  const int set = blockIdx.x, tid = threadIdx.x;
+  const int c0 = cand_off[set], nc = min(cand_off[set + 1] - c0, kWave);
+  const int t0 = set_off[set], kept = set_off[set + 1] - t0;
+  removal_list_offsets(recs, ent, c0, nc, tid, sh_begin, sh_roff);
+  const int raw = sh_roff[nc];
+  if (raw > kRemovalSetCap) return;  // (the whole workgroup: a large set)
+  int n2 = 1;
+  while (n2 < raw) n2 <<= 1;
+  for (int g = tid; g < n2; g += kRemovalThreads) {
+    uint64_t key = ~0ull;
+    if (g < raw) {
+      const int q = removal_position(sh_roff, nc, g);
+      key = removal_key(recs[sh_begin[q] + (g - sh_roff[q])].leaf, g);
+    }
+    sh_key[g] = key;
+  }
+  __syncthreads();
+  removal_bitonic_sort(sh_key, n2, tid);
   for (int g = tid; g < kept && g < raw; g += kRemovalThreads) {
     const uint64_t key = sh_key[g];
     const int idx = int(uint32_t(key));
-    const int q = position(idx);
+    const int q = removal_position(sh_roff, nc, idx);
     const kueue_tas_delta r = recs[sh_begin[q] + (idx - sh_roff[q])];
     if (r.leaf < 0) continue;  // (the host counted `kept` over leaf >= 0)
     kueue_tas_assumed o;
@@ -7399,6 +7419,143 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_table_kernel(const ku
     o.col = (r.col & kRemovalColMask) | (q << kRemovalPosShift);
     o.value = int64_t(0ull - uint64_t(r.delta));
     table[t0 + g] = o;
+  }
+}
+
+// ---- large sets: above kRemovalSetCap and up to KUEUE_TAS_REMOVAL_LARGE_SET_CAP
+// records.  The same table, built by several workgroups in launches the stream
+// orders (no workgroup waits on another):
+//   removal_chunk_sort_kernel   a workgroup per kRemovalSetCap-record chunk: the
+//                               chunk's keys sorted in LDS, to a global key buffer
+//   removal_merge_kernel        ceil(log2(chunks of the largest set)) passes
+//                               between two key buffers: adjacent runs pairwise
+//   removal_store_kernel        a workgroup per kRemovalExpandSegment table
+//                               records: the records, and the segment's counts
+//                               per position
+//   removal_seg_prefix_kernel   a wave per set: the counts' running sum over the
+//                               set's segments ("records of position q before")
+// large: [nl + 1] RemovalLargeSet, the last one the totals.  A block finds its
+// set by its chunk (or segment) number.
+__device__ __forceinline__ int removal_large_of(const RemovalLargeSet* large, int nl, int b, bool by_seg) {
+  int lo = 0, hi = nl - 1;  // the last l whose first chunk (segment) is <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((by_seg ? large[mid].seg_off : large[mid].chunk_off) <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kRemovalThreads) void removal_chunk_sort_kernel(const kueue_tas_delta* recs,
+                                                                             const int32_t* ent, const int32_t* cand_off,
+                                                                             const RemovalLargeSet* large, int nl,
+                                                                             uint64_t* keys) {
+  __shared__ uint64_t sh_key[kRemovalSetCap];
+  __shared__ int32_t sh_begin[kWave];
+  __shared__ int32_t sh_roff[kWave + 1];
+  const int tid = threadIdx.x;
+  const int l = removal_large_of(large, nl, int(blockIdx.x), false);
+  const RemovalLargeSet ls = large[l];
+  const int nkeys = large[l + 1].key_off - ls.key_off;  // the set's records as the host counted them
+  const int c0 = cand_off[ls.set], nc = min(cand_off[ls.set + 1] - c0, kWave);
+  removal_list_offsets(recs, ent, c0, nc, tid, sh_begin, sh_roff);
+  const int g0 = (int(blockIdx.x) - ls.chunk_off) * kRemovalSetCap;
+  const int cnt = min(min(sh_roff[nc], nkeys) - g0, kRemovalSetCap);
+  if (cnt <= 0) return;
+  int n2 = 1;
+  while (n2 < cnt) n2 <<= 1;  // (the tail chunk: padded with ~0)
+  for (int i = tid; i < n2; i += kRemovalThreads) {
+    uint64_t key = ~0ull;
+    if (i < cnt) {
+      const int g = g0 + i, q = removal_position(sh_roff, nc, g);
+      key = removal_key(recs[sh_begin[q] + (g - sh_roff[q])].leaf, g);
+    }
+    sh_key[i] = key;
+  }
+  __syncthreads();
+  removal_bitonic_sort(sh_key, n2, tid);
+  uint64_t* out = keys + ls.key_off + g0;
+  for (int i = tid; i < cnt; i += kRemovalThreads) out[i] = sh_key[i];
+}
+
+// One merge pass: the set's sorted runs of (1 << run_shift) keys, pairwise.
+// Keys are unique, so a key's place in the merged pair is its index in its own
+// run plus the sibling run's keys below it; an unpaired run (and a set that is
+// one run already) is copied.  A workgroup takes kRemovalSetCap keys.
+__global__ __launch_bounds__(kRemovalThreads) void removal_merge_kernel(const RemovalLargeSet* large, int nl,
+                                                                        const uint64_t* src, uint64_t* dst,
+                                                                        int run_shift) {
+  const int l = removal_large_of(large, nl, int(blockIdx.x), false);
+  const RemovalLargeSet ls = large[l];
+  const int nkeys = large[l + 1].key_off - ls.key_off;
+  const uint64_t* S = src + ls.key_off;
+  uint64_t* D = dst + ls.key_off;
+  const int g0 = (int(blockIdx.x) - ls.chunk_off) * kRemovalSetCap, g1 = min(g0 + kRemovalSetCap, nkeys);
+  for (int i = g0 + int(threadIdx.x); i < g1; i += kRemovalThreads) {
+    const uint64_t key = S[i];
+    const int r = i >> run_shift, r0 = r << run_shift, s0 = (r ^ 1) << run_shift;
+    int at = i;
+    if (s0 < nkeys) {
+      int lo = s0, hi = min(s0 + (1 << run_shift), nkeys);
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (S[mid] < key) lo = mid + 1;
+        else hi = mid;
+      }
+      at = min(r0, s0) + (i - r0) + (lo - s0);
+    }
+    if (at < nkeys) D[at] = key;
+  }
+}
+
+// The table records of one segment from the sorted keys, and the segment's
+// record counts per position (LDS counters; seg_prefix holds the counts until
+// removal_seg_prefix_kernel sums them).
+__global__ __launch_bounds__(kRemovalThreads) void removal_store_kernel(const kueue_tas_delta* recs, const int32_t* ent,
+                                                                        const int32_t* cand_off, const int32_t* set_off,
+                                                                        const RemovalLargeSet* large, int nl,
+                                                                        const uint64_t* keys, kueue_tas_assumed* table,
+                                                                        int32_t* seg_prefix) {
+  __shared__ int32_t sh_begin[kWave];
+  __shared__ int32_t sh_roff[kWave + 1];
+  __shared__ int32_t sh_hist[kWave];
+  const int tid = threadIdx.x;
+  const int l = removal_large_of(large, nl, int(blockIdx.x), true);
+  const RemovalLargeSet ls = large[l];
+  const int nkeys = large[l + 1].key_off - ls.key_off;
+  const int c0 = cand_off[ls.set], nc = min(cand_off[ls.set + 1] - c0, kWave);
+  const int t0 = set_off[ls.set], kept = min(set_off[ls.set + 1] - t0, nkeys);
+  if (tid < kWave) sh_hist[tid] = 0;
+  removal_list_offsets(recs, ent, c0, nc, tid, sh_begin, sh_roff);
+  const int raw = sh_roff[nc];
+  const int g0 = (int(blockIdx.x) - ls.seg_off) * kRemovalExpandSegment, g1 = min(g0 + kRemovalExpandSegment, kept);
+  for (int g = g0 + tid; g < g1; g += kRemovalThreads) {
+    const int idx = int(uint32_t(keys[ls.key_off + g]));
+    if (idx >= raw) continue;
+    const int q = removal_position(sh_roff, nc, idx);
+    const kueue_tas_delta r = recs[sh_begin[q] + (idx - sh_roff[q])];
+    if (r.leaf < 0) continue;  // (the host counted `kept` over leaf >= 0)
+    kueue_tas_assumed o;
+    o.leaf = r.leaf;
+    o.col = (r.col & kRemovalColMask) | (q << kRemovalPosShift);
+    o.value = int64_t(0ull - uint64_t(r.delta));
+    table[t0 + g] = o;
+    atomicAdd(&sh_hist[q], 1);
+  }
+  __syncthreads();
+  if (tid < kWave) seg_prefix[int64_t(blockIdx.x) * kWave + tid] = sh_hist[tid];
+}
+
+// One wave per large set: each position's counts summed over the set's
+// segments in order, exclusive.
+__global__ __launch_bounds__(kWave) void removal_seg_prefix_kernel(const RemovalLargeSet* large, int32_t* seg_prefix) {
+  const int s0 = large[blockIdx.x].seg_off, s1 = large[blockIdx.x + 1].seg_off;
+  int run = 0;
+  for (int s = s0; s < s1; s++) {
+    int32_t* p = seg_prefix + int64_t(s) * kWave + threadIdx.x;
+    const int v = *p;
+    *p = run;
+    run += v;
   }
 }
 
@@ -7410,12 +7567,16 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_table_kernel(const ku
 // record behind the kept records of lower leaves — into the evaluation's
 // reserved range of the batch's assumed records.  Nothing outside
 // [out_begin, out_end) is written.
-__global__ __launch_bounds__(kRemovalThreads) void removal_expand_kernel(const RemovalJob* jobs, const int32_t* set_off,
-                                                                         const kueue_tas_assumed* table,
-                                                                         kueue_tas_assumed* assumed) {
+// kSeg: the workgroup takes the tiles of one segment only (a large set's
+// table): the table records from seg_first on, up to kRemovalExpandSegment;
+// seg_base masked records lie before them; the own records behind every table
+// record are the last segment's.
+template <bool kSeg>
+__device__ __forceinline__ void removal_expand_body(const RemovalJob jb, const int32_t* set_off,
+                                                    const kueue_tas_assumed* table, kueue_tas_assumed* assumed,
+                                                    int seg_first, int seg_base, bool seg_last) {
   __shared__ int32_t sh_excl[kRemovalExpandTile];
   __shared__ int32_t sh_wave[kRemovalThreads / kWave];
-  const RemovalJob jb = jobs[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
   const int tn = set_off[jb.set + 1] - set_off[jb.set];
   const kueue_tas_assumed* T = table + set_off[jb.set];
@@ -7423,13 +7584,14 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_expand_kernel(const R
   const int own_n = jb.own_end - jb.own_begin;
   kueue_tas_assumed* out = assumed + jb.out_begin;
   const int cap = jb.out_end - jb.out_begin;
-  int base = 0;  // kept records of the tiles before
-  for (int ts = 0; ts < tn; ts += kRemovalExpandTile) {
+  const int ts_end = kSeg ? min(tn, seg_first + kRemovalExpandSegment) : tn;
+  int base = kSeg ? seg_base : 0;  // kept records of the tiles before
+  for (int ts = kSeg ? seg_first : 0; ts < ts_end; ts += kRemovalExpandTile) {
     const int t = ts + tid;
     kueue_tas_assumed r;
     r.leaf = 0, r.col = 0, r.value = 0;
     bool keep = false;
-    if (t < tn) {
+    if (t < ts_end) {
       r = T[t];
       keep = ((jb.mask >> ((uint32_t(r.col) >> kRemovalPosShift) & 63u)) & 1ull) != 0;
     }
@@ -7451,14 +7613,14 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_expand_kernel(const R
         else hi = mid;
       }
       const int pos = base + ex + lo;
-      if (pos < cap) {
+      if ((!kSeg || pos >= 0) && pos < cap) {
         r.col &= kRemovalColMask;
         out[pos] = r;
       }
     }
     __syncthreads();
     // the own records whose first table record of an equal or higher leaf lies in this tile
-    const int te = min(ts + kRemovalExpandTile, tn);
+    const int te = min(ts + kRemovalExpandTile, ts_end);
     for (int j = tid; j < own_n; j += kRemovalThreads) {
       const kueue_tas_assumed o = own[j];
       int lo = 0, hi = tn;
@@ -7469,12 +7631,13 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_expand_kernel(const R
       }
       if (lo >= ts && lo < te) {
         const int pos = j + base + sh_excl[lo - ts];
-        if (pos < cap) out[pos] = o;
+        if ((!kSeg || pos >= 0) && pos < cap) out[pos] = o;
       }
     }
     base += total;
     __syncthreads();
   }
+  if (kSeg && !seg_last) return;
   for (int j = tid; j < own_n; j += kRemovalThreads) {  // own records behind every table record
     const kueue_tas_assumed o = own[j];
     int lo = 0, hi = tn;
@@ -7485,9 +7648,36 @@ __global__ __launch_bounds__(kRemovalThreads) void removal_expand_kernel(const R
     }
     if (lo == tn) {
       const int pos = j + base;
-      if (pos < cap) out[pos] = o;
+      if ((!kSeg || pos >= 0) && pos < cap) out[pos] = o;
     }
   }
+}
+
+__global__ __launch_bounds__(kRemovalThreads) void removal_expand_kernel(const RemovalJob* jobs, const int32_t* set_off,
+                                                                         const kueue_tas_assumed* table,
+                                                                         kueue_tas_assumed* assumed) {
+  removal_expand_body<false>(jobs[blockIdx.x], set_off, table, assumed, 0, 0, true);
+}
+
+// removal_expand_seg_kernel: one workgroup per (masked evaluation of a large
+// set, segment of its table).  segs[b] = (job, the segment's first table
+// record, its row of seg_prefix, 1: the set's last segment); the segment's
+// first output index is the sum of the masked positions' prefix counts.
+__global__ __launch_bounds__(kRemovalThreads) void removal_expand_seg_kernel(const RemovalJob* jobs, const int4* segs,
+                                                                             const int32_t* set_off,
+                                                                             const kueue_tas_assumed* table,
+                                                                             const int32_t* seg_prefix,
+                                                                             kueue_tas_assumed* assumed) {
+  __shared__ int32_t sh_base;
+  const int4 sg = segs[blockIdx.x];
+  const RemovalJob jb = jobs[sg.x];
+  if (threadIdx.x < kWave) {
+    int v = ((jb.mask >> threadIdx.x) & 1ull) ? seg_prefix[int64_t(sg.z) * kWave + threadIdx.x] : 0;
+    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    if (threadIdx.x == 0) sh_base = v;
+  }
+  __syncthreads();
+  removal_expand_body<true>(jb, set_off, table, assumed, sg.y, sh_base, sg.w != 0);
 }
 
 }  // namespace ktas

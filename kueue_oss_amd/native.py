@@ -76,8 +76,9 @@ EXPORTED_SYMBOLS = [
     "kueue_tas_host_usage_deltas", "kueue_tas_host_last_admit_block_path", "kueue_tas_host_column_generation",
     "kueue_tas_snapshot_digest", "kueue_tas_snapshot_read_leaves", "kueue_tas_last_digest_ms",
     "kueue_tas_host_snapshot_digest", "kueue_tas_host_verify_device",
-    "kueue_tas_removal_tables_build", "kueue_tas_removal_tables_clear", "kueue_tas_eval_batch_removals",
-    "kueue_tas_removal_stats", "kueue_tas_host_preemption_search_batch", "kueue_tas_host_last_search_stats",
+    "kueue_tas_removal_tables_build", "kueue_tas_removal_tables_build_flags", "kueue_tas_removal_tables_clear",
+    "kueue_tas_eval_batch_removals", "kueue_tas_removal_stats", "kueue_tas_removal_large_stats",
+    "kueue_tas_host_preemption_search_batch", "kueue_tas_host_last_search_stats",
 ]
 
 # the Makefile's SRC_HASH inputs, in order
@@ -678,7 +679,7 @@ class TASFlavorSnapshot:
                     "recordsExpanded", "wallUs")
 
     def preemption_search_batch(self, ids, workloads, candidates, assign: bool = False,
-                                host_overlays: bool = False) -> dict:
+                                host_overlays: bool = False, large_sets: bool = True) -> dict:
         """The preemption search of a cycle (kueue_tas_host_preemption_search_batch):
         ``ids`` the preempting heads (compiled workloads, compile()),
         ``workloads`` the preemptable workloads as for admit_block (DELTA_DTYPE
@@ -693,7 +694,10 @@ class TASFlavorSnapshot:
         WithSimulateEmpty without a fitting prefix) are what last_assignments()
         and last_results() return, under ``ids``.  ``host_overlays`` expands
         every removal on the host (the path of preemptors with more than 64
-        candidates) instead of on the device."""
+        candidates) instead of on the device.  ``large_sets=False``
+        (KUEUE_TAS_PS_SMALL_SETS_ONLY) keeps only the sets of at most
+        abi.REMOVAL_SET_CAP records on the device; by default sets of up to
+        abi.REMOVAL_LARGE_SET_CAP records are built there."""
         import numpy as np
         td, toff = self._target_table(workloads)
         pid = np.ascontiguousarray(ids, dtype=np.int32)
@@ -708,7 +712,8 @@ class TASFlavorSnapshot:
         etg = np.zeros(max(cand.size, 1), dtype=np.int32)
         rc = self._lib.kueue_tas_host_preemption_search_batch(
             self._h, pid.ctypes.data, pid.size, td.ctypes.data, toff.ctypes.data, len(toff) - 1, cand.ctypes.data,
-            coff.ctypes.data, (1 if assign else 0) | (2 if host_overlays else 0), pf.ctypes.data, first.ctypes.data,
+            coff.ctypes.data, (1 if assign else 0) | (2 if host_overlays else 0) | (0 if large_sets else 4), pf.ctypes.data,
+            first.ctypes.data,
             eoff.ctypes.data, etg.ctypes.data)
         if rc:
             raise RuntimeError(f"kueue_tas_host_preemption_search_batch failed ({rc}): {self._err()}")
